@@ -46,6 +46,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP64_PEAK_TFLOPS = 78.6  # MI355X FP64 vector peak; the sweep has no matrix work
 FLOP_PER_PAIR = 60.0     # ~45 FP64 flop + exp + rsqrt per directed pair of a sweep
 L2_GATHER_TBS = (16.8, 18.8)  # MI355X_MICROARCH.md: chip-wide rate of L2-served 64-byte row gathers (66-73 GB/s per CU x 256)
+DUMP_MAX_BYTES = 60 << 20   # --dump-outputs: under 64 MB in all
 FIXED30 = ["fixed_iteration", "yes", "max_iterations", "30"]
 PREC11 = ["fixed_iteration", "no", "precision", "1e-11", "max_iterations", "100"]
 CONFIGS = {  # BASELINE.json configs[k] -> replication of the 1,349-atom MOF5+H2 cell, solver keywords
@@ -97,6 +98,26 @@ def timed_steps(torch, p, steps, warmup):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     return out, dt, ms_solve, launches
+
+
+def dump_outputs(where, p, s, out):
+    """What a caller of the resident path receives from the last timed step, in float64: the forces on local and ghost atoms
+    and the converged dipoles (caller order, downloaded from the device), the energies and the virial."""
+    os.makedirs(where, exist_ok=True)
+    arrays = {
+        "f": p.download("f", 3 * (s.nlocal + s.nghost)).reshape(-1, 3),
+        "mu": p.download("mu", 3 * s.nlocal).reshape(-1, 3),
+        "energies": np.array([out["eng_vdwl"], out["eng_coul"], out["eng_pol"]], dtype=np.float64),   # E_vdwl, E_coul, E_pol
+        "virial": np.asarray(out["virial"], dtype=np.float64),
+    }
+    if sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES:   # a large box: the same seeded sample of rows every run
+        for name in ("f", "mu"):
+            a = arrays[name]
+            keep = min(a.shape[0], DUMP_MAX_BYTES // 64)   # 32 bytes per kept row (3 values + its index), two arrays
+            rows = np.sort(np.random.default_rng(12345).choice(a.shape[0], size=keep, replace=False))
+            arrays[name], arrays[name + "_rows"] = a[rows], rows.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(where, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def roofline(s, out, ms_solve, launches, steps, pkg):
@@ -591,9 +612,15 @@ def main():
     ap.add_argument("--extra", nargs="*", default=[], help="extra pair_style keywords (experiments)")
     ap.add_argument("--direct", action="store_true", help="N = 1: run in THIS process (profilers, scripts); default: a budgeted child of the launcher")
     ap.add_argument("--schedule", default="", help=f"N > 1: how the ranks exchange the halo dipoles, one of {sorted(SCHEDULES)} (default: legacy)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last one computed (forces, dipoles, energies, virial) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit("bench.py: --dump-outputs covers the one-GPU path (--gpus 1)")
     if args.schedule and args.schedule not in SCHEDULES:
         raise SystemExit(f"bench.py: --schedule is one of {sorted(SCHEDULES)}")
     if "WORLD_SIZE" not in os.environ and not args.direct:
@@ -633,6 +660,8 @@ def main():
         workload = describe(cfg, s.nlocal)
     p = pkg.pair_from_system(s, device=0)
     out, dt, ms_solve, launches = timed_steps(torch, p, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, p, s, out)
     p.close()
     n = s.nlocal
     config = {"workload": workload, "natoms": n, "sweeps": out["sweeps"], "iterations": out["iterations"], "colors": out["ncolors"],

@@ -7,7 +7,9 @@ import subprocess
 import sys
 import textwrap
 import time
+from types import SimpleNamespace
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -182,3 +184,34 @@ def test_an_explicit_schedule_runs_that_job_alone(tmp_path, monkeypatch):
                       make_cmd=lambda name, extra: (seen.append((name, list(extra))) or ok), out=out)
     assert rc == 0 and seen == [("lag1", ["--schedule", "lag1"])]
     assert list(json.loads(out.getvalue())["config"]["schedules"]) == ["lag1"]
+
+
+@pytest.mark.parametrize("argv,msg", [(["--steps", "0"], "--steps must be >= 1"),
+                                      (["--gpus", "2", "--dump-outputs", "x"], "--dump-outputs covers the one-GPU path")])
+def test_argument_errors_stop_before_any_work(argv, msg, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    monkeypatch.setattr(bench, "launch", lambda *a, **k: pytest.fail("launched"))
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert msg in str(e.value)
+
+
+def test_dump_outputs_writes_what_the_last_step_returned_in_float64(tmp_path, monkeypatch):
+    class Pair:   # stands in for PolarPair after the timed steps: download(name, n) -> n doubles
+        def download(self, name, n):
+            return np.arange(n, dtype=np.float64) * (1.0 if name == "f" else -1.0)
+
+    out = {"eng_vdwl": 1.5, "eng_coul": -2.5, "eng_pol": -0.25, "virial": np.arange(6.0)}
+    bench.dump_outputs(str(tmp_path / "a"), Pair(), SimpleNamespace(nlocal=40, nghost=10), out)
+    got = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert sorted(got) == ["energies", "f", "mu", "virial"] and all(a.dtype == np.float64 for a in got.values())
+    assert got["f"].shape == (50, 3) and got["mu"].shape == (40, 3)
+    assert list(got["energies"]) == [1.5, -2.5, -0.25] and list(got["virial"]) == list(range(6))
+    # a box too large for the cap: the same seeded sample of rows, every run, under the cap
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 64 * 20)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), Pair(), SimpleNamespace(nlocal=40, nghost=10), out)
+    b, c = ({p.stem: np.load(p) for p in (tmp_path / d).glob("*.npy")} for d in ("b", "c"))
+    assert sorted(b) == ["energies", "f", "f_rows", "mu", "mu_rows", "virial"]
+    assert all(np.array_equal(b[k], c[k]) for k in b) and b["f"].shape == (20, 3)
+    assert np.array_equal(b["f"][:, 0], 3 * b["f_rows"]) and sum(a.nbytes for k, a in b.items() if k[0] in "fm") <= 64 * 20

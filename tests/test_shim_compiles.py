@@ -1,6 +1,7 @@
 """The LAMMPS-side files (the Pair shim and the atom style that carries the polarization attributes) must compile to
 objects against the reference's headers as they are, reference nothing outside LAMMPS' core and the C-ABI, and link
-against libpolar_mi355x.so.  Build container only: /root/reference does not exist on the GPU box, where this skips."""
+against libpolar_mi355x.so.  The objects are compiled by build() (oracle/Makefile `ref`, into oracle/_ref/shim/) where the
+reference's sources are present; without them this skips."""
 import os
 import re
 import subprocess
@@ -8,13 +9,12 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src"
 PKG = os.path.join(ROOT, "lammps-induced-dipole-polarization-pair-style_amd")
-SHIM = [os.path.join(ROOT, "lammps_shim", f) for f in
-        ("pair_lj_cut_coul_long_polarization_mi355x.cpp", "atom_vec_full_polar.cpp")]
-INC = [f"-I{REF}", f"-I{REF}/MOLECULE", f"-I{REF}/STUBS", f"-I{ROOT}/include"]
+OBJS = [os.path.join(ROOT, "oracle", "_ref", "shim", f) for f in
+        ("pair_lj_cut_coul_long_polarization_mi355x.o", "atom_vec_full_polar.o")]
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference headers not present")
+pytestmark = pytest.mark.skipif(not all(os.path.exists(o) for o in OBJS),
+                                reason="oracle/_ref/shim not built (build() makes it where the reference's sources are present)")
 
 # what a LAMMPS executable provides besides its own classes: MPI (or src/STUBS) and the C / C++ runtime libraries
 def _runtime_exports():
@@ -33,15 +33,7 @@ def _runtime_exports():
 
 @pytest.fixture(scope="module")
 def objects(tmp_path_factory):
-    d = tmp_path_factory.mktemp("shim")
-    objs = []
-    for src in SHIM:
-        o = str(d / (os.path.basename(src)[:-4] + ".o"))
-        r = subprocess.run(["g++", "-c", "-fPIC", "-O2", "-std=c++11", "-Wall"] + INC + [src, "-o", o],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        objs.append(o)
-    return d, objs
+    return tmp_path_factory.mktemp("shim"), list(OBJS)
 
 
 def _undefined(path):
