@@ -83,6 +83,15 @@ typedef struct {
    * |r_k - sum gamma_j (r_{k-j+1} - r_{k-j})|: the same fixed point, the same stop rule on |G(mu_k) - mu_k| (PS.cpp:1194-1210),
    * fewer sweeps.  Per sweep it adds m dot products over 3N doubles; across ranks they ride the stop rule's all-reduce. */
   int polar_accel;
+  /* polar_ewald <accuracy> (extension keyword; 0 = off, the default, the reference's static field): the static field that
+   * polarizes the atoms becomes the Ewald-summed (tin-foil) field of all charge images, in line with the Ewald real-space
+   * charge-charge energy of this style plus a KSpace style -- real space erfc(g r) over the pairs within cut_coul, the erf
+   * part taken off the excluded same-molecule pairs (minimum image, r <= cut_coul), and a direct k-vector sum over
+   * 0 < |k| <= k_cut = 2 g sqrt(-ln accuracy) (exp(-k^2/4g^2) <= accuracy), g = the g_ewald of polar_pair_init /
+   * polar_set_coul.  The charge-dipole forces and the virial are the gradient of that field at fixed dipoles.  0 < accuracy
+   * < 1 (typical 1e-6).  Single handle, periodic boxes, exact or list mode; refused (POLAR_ERR_UNSUPPORTED) on a row-sharded
+   * handle, by the polar_dist_* driver, with rccl_halo and with a per-atom virial (vflag & 4). */
+  double polar_ewald;
 } polar_settings;
 #define POLAR_ACCEL_MAX 8
 
@@ -101,6 +110,9 @@ typedef struct {
   long long dd_pairs;                 /* entries of the dipole-dipole list swept per sweep */
   double ms_color_host;               /* host wall time of the colour-phase rebuild (conflict graph + DSATUR) when this
                                          step rebuilt it (reneighbor steps in list mode), else 0 */
+  double ms_kspace;                   /* `polar_ewald`: device time of the reciprocal-space kernels (field + forces; the host-side
+                                         rebuild of the k-vector set when the box or g_ewald changed is not in it), else 0 */
+  int nkvec;                          /* `polar_ewald`: k-vectors of the half space summed over, else 0 */
 } polar_result;
 
 /* ---- lifetime --------------------------------------------------------------------------- */

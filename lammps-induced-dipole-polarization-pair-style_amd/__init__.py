@@ -92,7 +92,8 @@ class Settings(C.Structure):
                 ("polar_damp", C.c_double), ("polar_gamma", C.c_double), ("iterations_max", C.c_int),
                 ("damping_type", C.c_int), ("zodid", C.c_int), ("fixed_iteration", C.c_int), ("polar_gs", C.c_int),
                 ("polar_gs_ranked", C.c_int), ("use_previous", C.c_int), ("debug", C.c_int), ("dd_cutoff", C.c_double),
-                ("device_neigh", C.c_int), ("restart_polar", C.c_int), ("deterministic", C.c_int), ("polar_sor", C.c_double), ("rccl_halo", C.c_int), ("polar_accel", C.c_int)]
+                ("device_neigh", C.c_int), ("restart_polar", C.c_int), ("deterministic", C.c_int), ("polar_sor", C.c_double), ("rccl_halo", C.c_int), ("polar_accel", C.c_int),
+                ("polar_ewald", C.c_double)]
 
 
 class Result(C.Structure):
@@ -101,7 +102,7 @@ class Result(C.Structure):
                 ("rms_dmu", C.c_double), ("iterations", C.c_int), ("sweeps", C.c_int), ("status", C.c_int),
                 ("ncolors", C.c_int), ("ms_total", C.c_double), ("ms_rank", C.c_double), ("ms_ljcoul", C.c_double),
                 ("ms_static", C.c_double), ("ms_solve", C.c_double), ("ms_force", C.c_double), ("ms_list", C.c_double),
-                ("dd_pairs", C.c_longlong), ("ms_color_host", C.c_double)]
+                ("dd_pairs", C.c_longlong), ("ms_color_host", C.c_double), ("ms_kspace", C.c_double), ("nkvec", C.c_int)]
 
 
 _dp, _ip, _llp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_longlong)
@@ -411,6 +412,8 @@ class PolarPair:
             args += ["polar_sor", repr(float(st.polar_sor))]
         if getattr(st, "polar_accel", 0):
             args += ["polar_accel", str(int(st.polar_accel))]
+        if getattr(st, "polar_ewald", 0.0):
+            args += ["polar_ewald", repr(float(st.polar_ewald))]
         self.settings(args)
         if modify_args:
             self.modify(list(modify_args))

@@ -26,6 +26,10 @@ namespace polar {
 struct InputError : std::runtime_error {
   explicit InputError(const char *m) : std::runtime_error(m) {}
 };
+// a mode the library does not offer (POLAR_ERR_UNSUPPORTED)
+struct Unsupported : std::runtime_error {
+  explicit Unsupported(const char *m) : std::runtime_error(m) {}
+};
 
 inline void settings_defaults(polar_settings &s) {  // PS.cpp:65-78
   s.cut_lj_global = 0.0;
@@ -48,6 +52,7 @@ inline void settings_defaults(polar_settings &s) {  // PS.cpp:65-78
   s.polar_sor = 1.0;
   s.rccl_halo = 0;
   s.polar_accel = 0;
+  s.polar_ewald = 0.0;
 }
 
 // Force::numeric / Force::inumeric behaviour: whole token must parse.
@@ -155,6 +160,10 @@ class PairHost {
       else if (strcmp("polar_accel", k) == 0) {                               // extension keyword
         st.polar_accel = inumeric(v);
         if (st.polar_accel < 0 || st.polar_accel > POLAR_ACCEL_MAX) throw InputError("Illegal pair_style command");
+      }
+      else if (strcmp("polar_ewald", k) == 0) {                               // extension keyword
+        st.polar_ewald = numeric(v);
+        if (!(st.polar_ewald >= 0.0 && st.polar_ewald < 1.0)) throw InputError("Illegal pair_style command");
       }
       else if (strcmp("polar_sor", k) == 0) {                                 // extension keyword
         st.polar_sor = numeric(v);

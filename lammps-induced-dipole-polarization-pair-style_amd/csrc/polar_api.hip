@@ -207,6 +207,7 @@ int polar_create(int device, polar_handle **out) {
     HIPCHECK(hipEventCreateWithFlags(&h->ev_dl0, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_dl1, hipEventDisableTiming));
     HIPCHECK(hipEventCreateWithFlags(&h->ev_mu_ready, hipEventDisableTiming));
     for (auto &e : h->ev_fchunk) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (auto &e : h->ev_ks) HIPCHECK(hipEventCreate(&e));
     HIPCHECK(hipStreamCreateWithFlags(&h->dl_stream, hipStreamNonBlocking));
     if (getenv("POLAR_NO_OVERLAP")) h->overlap_lj = false;
     if (const char *e = getenv("POLAR_LJ_PERS")) h->lj_pers = atoi(e);
@@ -230,6 +231,7 @@ int polar_destroy(polar_handle *h) {
     (void)hipStreamSynchronize(h->stream);
     if (h->lj_stream) { (void)hipStreamSynchronize(h->lj_stream); (void)hipStreamDestroy(h->lj_stream); }
     for (hipEvent_t e : {h->ev_fork, h->ev_join, h->ev_lj0, h->ev_lj1, h->ev_dl0, h->ev_dl1, h->ev_mu_ready}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->ev_ks) if (e) (void)hipEventDestroy(e);
     if (h->dl_stream) (void)hipStreamDestroy(h->dl_stream);
     if (h->up_stream) { (void)hipStreamSynchronize(h->up_stream); (void)hipStreamDestroy(h->up_stream); }
     if (h->ev_list_up) (void)hipEventDestroy(h->ev_list_up);
@@ -248,7 +250,7 @@ int polar_destroy(polar_handle *h) {
     h->d_mol_s.release(); h->d_perm.release(); h->d_inv.release(); h->d_rows_orig.release(); h->d_ownrows.release(); h->d_ef_s.release(); h->d_scan_a.release(); h->d_scan_b.release(); h->d_gs_cnt.release(); h->d_T6.release(); h->d_Minv.release(); h->d_gsN.release(); h->d_gsAT.release(); h->d_cb.release(); h->d_gs_part.release();
     h->d_rec0.release(); h->d_rec1.release(); h->d_scal.release(); h->d_slots.release();
     h->d_cell_id.release(); h->d_cell_cnt.release(); h->d_cell_fill.release();
-    h->d_nl_cnt.release(); h->d_dd_cnt.release(); h->d_dd_wrap.release(); h->d_lpdesc.release(); h->d_slot.release(); h->d_color_orig.release(); h->d_color_s.release(); h->d_trace.release(); h->d_cl_orig.release(); h->d_cl_cnt.release(); h->d_cl_wrap.release(); h->d_cl_tw.release(); h->d_cl_s.release(); h->d_nl_j.release(); h->d_dd_j.release();
+    h->d_nl_cnt.release(); h->d_dd_cnt.release(); h->d_dd_wrap.release(); h->d_lpdesc.release(); h->d_slot.release(); h->d_color_orig.release(); h->d_color_s.release(); h->d_trace.release(); h->d_ew_kv.release(); h->d_ew_hkl.release(); h->d_ew_rows.release(); h->d_ew_s.release(); h->d_ew_m.release(); h->d_ew_part.release(); h->d_ew_erec.release(); h->d_ew_vpart.release(); h->d_ew_out.release(); h->d_cl_orig.release(); h->d_cl_cnt.release(); h->d_cl_wrap.release(); h->d_cl_tw.release(); h->d_cl_s.release(); h->d_nl_j.release(); h->d_dd_j.release();
     h->d_cell_first.release(); h->d_nl_first.release(); h->d_dd_first.release(); h->d_dd_s.release(); h->d_xq.release(); h->d_pos4.release();
     h->d_overflow.release(); h->d_ddtot.release();
     h->d_cadj.release(); h->d_cdeg.release(); h->d_ccnt.release(); h->d_cflags.release(); h->d_crelabel.release(); h->d_klist.release(); h->d_dbgf.release(); h->d_ulead.release(); h->d_udd_j.release(); h->d_upos.release(); h->d_unit.release(); h->d_udesc.release(); h->d_cprio.release(); h->d_cstat.release(); h->d_coff.release(); h->d_lp_pend.release(); h->d_lp_part.release();
@@ -395,6 +397,7 @@ int polar_set_settings(polar_handle *h, const polar_settings *s) {
     if (v.polar_sor == 0.0) v.polar_sor = 1.0;   // a zero-initialised struct means "the reference's update", not "freeze the dipoles"
     if (!(v.polar_sor > 0.0 && v.polar_sor < 2.0)) throw InputError("polar_sor must lie in (0, 2)");
     if (v.polar_accel < 0 || v.polar_accel > POLAR_ACCEL_MAX) throw InputError("polar_accel must lie in 0 .. 8");
+    if (!(v.polar_ewald >= 0.0 && v.polar_ewald < 1.0)) throw InputError("polar_ewald must lie in [0, 1)");
     h->ph.st = v;
     h->colors_valid = false;
     return POLAR_OK;

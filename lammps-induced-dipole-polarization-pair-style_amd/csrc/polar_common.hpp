@@ -396,4 +396,21 @@ __device__ __forceinline__ void tensor_scalars_k(double r2, double pd, const Exp
   }
 }
 
+
+// `polar_ewald`: the radial factors of the real-space Ewald field E = q B1(r) del and of its gradient
+// dE_a/ddel_b = q (B1 delta_ab - B2 del_a del_b):  B1 = (erfc(g r)/r + 2g/sqrt(pi) e^{-g^2 r^2}) / r^2,
+// B2 = (3 B1 + 2g/sqrt(pi) 2 g^2 e^{-g^2 r^2}) / r^2.  An excluded pair (kept = false) takes the erf part off instead:
+// B1 - 1/r^3 and B2 - 3/r^5, written with erf so that short intramolecular distances keep their digits.
+__device__ __forceinline__ double ewald_b1(double rsq, double g, bool kept) {
+  const double r = sqrt(rsq), r2inv = 1.0 / rsq;
+  const double e = 1.1283791670955126 * g * exp(-g * g * rsq);   // 2g/sqrt(pi) e^{-g^2 r^2}
+  return kept ? (erfc(g * r) / r + e) * r2inv : -(erf(g * r) / r - e) * r2inv;
+}
+__device__ __forceinline__ void ewald_b12(double rsq, double g, bool kept, double &b1, double &b2) {
+  const double r = sqrt(rsq), r2inv = 1.0 / rsq;
+  const double e = 1.1283791670955126 * g * exp(-g * g * rsq);
+  b1 = kept ? (erfc(g * r) / r + e) * r2inv : -(erf(g * r) / r - e) * r2inv;
+  b2 = (3.0 * b1 + 2.0 * g * g * e) * r2inv;
+}
+
 }  // namespace polar

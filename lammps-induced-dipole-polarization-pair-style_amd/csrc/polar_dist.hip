@@ -178,6 +178,7 @@ int dist_guarded(polar_dist *d, F &&fn) {
   try {
     return fn();
   } catch (const InputError &e) { d->err = e.what(); return POLAR_ERR_INPUT;
+  } catch (const Unsupported &e) { d->err = e.what(); return POLAR_ERR_UNSUPPORTED;
   } catch (const NoDevice &e) { d->err = e.what(); return POLAR_ERR_NO_DEVICE;
   } catch (const HipError &e) { d->err = e.what(); return POLAR_ERR_HIP;
   } catch (const std::exception &e) { d->err = e.what(); return POLAR_ERR_STATE; }
@@ -481,6 +482,9 @@ int polar_dist_step(polar_dist *d, polar_handle *h, int eflag, int vflag, polar_
     HIPCHECK(hipSetDevice(h->device));
     RcclApi &R = rccl();
     const polar_settings &st = h->ph.st;
+    // (every rank holds the same keywords: all of them refuse here, before the first collective)
+    if (st.polar_ewald > 0.0)
+      throw Unsupported("polar_ewald is not offered by the multi-GPU driver: the structure factors would need an all-reduce across the ranks");
     const bool gs = st.polar_gs || st.polar_gs_ranked;
     const int max_sweeps = st.iterations_max + 1;
     int rc = POLAR_OK;
@@ -498,6 +502,7 @@ int polar_dist_step(polar_dist *d, polar_handle *h, int eflag, int vflag, polar_
         if (st.polar_accel > 0 && deterministic(h)) throw InputError("polar_accel and `deterministic yes` exclude each other");
         step_begin_lists(h, eflag, vflag);
       } catch (const InputError &e) { brc = POLAR_ERR_INPUT; berr = e.what();
+      } catch (const Unsupported &e) { brc = POLAR_ERR_UNSUPPORTED; berr = e.what();
       } catch (const NoDevice &e) { brc = POLAR_ERR_NO_DEVICE; berr = e.what();
       } catch (const HipError &e) { brc = POLAR_ERR_HIP; berr = e.what();
       } catch (const std::exception &e) { brc = POLAR_ERR_STATE; berr = e.what(); }

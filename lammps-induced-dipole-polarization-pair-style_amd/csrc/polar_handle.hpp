@@ -310,6 +310,15 @@ struct polar_handle {
   std::vector<double> h_tmp;
   double *h_stage = nullptr;  // pinned staging area for downloads
   DBuf<double> d_trace;       // `debug yes`: u_polar after every sweep of the last solve
+  // `polar_ewald` (polar_ewald.hpp): the k-vector set of the last box / g_ewald / accuracy (rebuilt when one of them changes),
+  // structure factors S and M, chunk partials, the reciprocal field (s space), workgroup partials, [u_ef, virial[6]]
+  DBuf<double4> d_ew_kv; DBuf<int4> d_ew_hkl, d_ew_rows;
+  DBuf<double2> d_ew_s, d_ew_m, d_ew_part;
+  DBuf<double> d_ew_erec, d_ew_vpart, d_ew_out;
+  std::vector<double> ew_key;
+  int ew_nk = 0, ew_nrow = 0, ew_nm = 0;
+  double ew_cell[6] = {0, 0, 0, 0, 0, 0};
+  hipEvent_t ev_ks[4] = {nullptr, nullptr, nullptr, nullptr};
   int ntrace = 0;
   size_t h_stage_cap = 0;
 };
@@ -325,6 +334,8 @@ int guarded(polar_handle *h, F &&fn) {
     return fn();
   } catch (const InputError &e) {
     return fail(h, POLAR_ERR_INPUT, e.what());
+  } catch (const Unsupported &e) {
+    return fail(h, POLAR_ERR_UNSUPPORTED, e.what());
   } catch (const NoDevice &e) {
     return fail(h, POLAR_ERR_NO_DEVICE, e.what());
   } catch (const HipError &e) {
@@ -447,6 +458,7 @@ inline int own_lo(const polar_handle *h) { return h->row_lo; }
 inline int own_n(const polar_handle *h) { return (h->row_hi < 0 ? h->nlocal : h->row_hi) - h->row_lo; }
 inline int norm_count(const polar_handle *h) { return (int)(h->global_count > 0 ? h->global_count : h->nlocal); }
 inline bool sharded(const polar_handle *h) { return own_n(h) != h->nlocal; }
+inline bool ewald_on(const polar_handle *h) { return h->ph.st.polar_ewald > 0.0; }  // `polar_ewald` (polar_ewald.hpp)
 // the dd rows of the current lists sit in the launch order of the colouring in force (a colouring rebuilt after the
 // lists were laid out -- a clash found on a reneighbor step, a changed alpha pattern -- makes them stale)
 inline bool slots_current(const polar_handle *h) { return h->slots_by_color && h->slots_epoch == h->color_epoch; }

@@ -21,7 +21,8 @@
 // polar_rows.hpp (the per-row kernels of a step), polar_solver.hpp (the dipole solver: list-mode sweep, loop control),
 // polar_exact.hpp (exact mode's exact-order Gauss-Seidel), polar_accel.hpp (Anderson mixing, `polar_accel`),
 // polar_lists.hpp (list mode: cells, neighbor lists, exchange), polar_tiles.hpp (list mode: the tile sweep
-// -- one workgroup per cell, neighbour records staged in LDS -- and its builder).
+// -- one workgroup per cell, neighbour records staged in LDS -- and its builder), polar_ewald.hpp (`polar_ewald`: the
+// reciprocal-space static field and charge-dipole forces).
 #pragma once
 
 #include "polar_common.hpp"
@@ -31,3 +32,4 @@
 #include "polar_accel.hpp"
 #include "polar_lists.hpp"
 #include "polar_tiles.hpp"
+#include "polar_ewald.hpp"

@@ -446,15 +446,21 @@ static __global__ __launch_bounds__(POLAR_LJ_PERS_THREADS) void k_ljcoul_pers(LJ
 // a4 + a5  static field (shifted-force Coulomb, PS.cpp:324-361), unit scale and initial guess
 // (PS.cpp:363-386).  Full-row evaluation: E_i = sum_j ef_temp * q_j * del_ij, which is the
 // reference's i<j scatter seen from row i (del is antisymmetric under the image rule).
-template <bool ALLPAIRS>
-static __global__ __launch_bounds__(POLAR_BLOCK) void k_static_field(const int *__restrict__ rows, int nrows, int nlocal,
+// EW (`polar_ewald`): the real-space half of the Ewald field instead -- q_j B1(r) del over the kept pairs within cut_coul and
+// q_j (B1(r) - 1/r^3) del (the erf part taken off) over the excluded same-molecule ones; the reciprocal field erec (s space)
+// is added before the initial guess.
+// (one body, two kernels: the EW form -- erfc / erf per pair -- needs far more registers than the 64 of k_static_field, so
+//  it is a kernel of its own, k_ew_static_field, and k_static_field is the same code as without the keyword)
+template <bool ALLPAIRS, bool EW>
+static __device__ __forceinline__ void static_field_body(const int *__restrict__ rows, int nrows, int nlocal,
                                                               const AtomRec *__restrict__ rec,
                                                               const int *__restrict__ mol, Box box,
                                                               RowList nl,
                                                               const int *__restrict__ nl_j, double cut_coulsq,
                                                               double e2s, double gamma, int use_previous,
                                                               double *__restrict__ ef, AtomRec *__restrict__ rec0,
-                                                              AtomRec *__restrict__ rec1, const double4 *__restrict__ xq_s) {
+                                                              AtomRec *__restrict__ rec1, const double4 *__restrict__ xq_s,
+                                                              double g_ewald, const double *__restrict__ erec) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * POLAR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (row >= nrows) return;
@@ -473,7 +479,12 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_static_field(const int *
       double dx, dy, dz;
       pair_del<ALLPAIRS>(box, ri.x, ri.y, ri.z, rj.x, rj.y, rj.z, dx, dy, dz);
       const double rsq = dx * dx + dy * dy + dz * dz;
-      if (rsq <= cut_coulsq && ((mi != mol[j]) || mi == 0)) {  // note <=, PS.cpp:342
+      if (EW) {
+        if (rsq <= cut_coulsq) {
+          const double ef_temp = ewald_b1(rsq, g_ewald, (mi != mol[j]) || mi == 0) * rj.q;
+          ex += ef_temp * dx; ey += ef_temp * dy; ez += ef_temp * dz;
+        }
+      } else if (rsq <= cut_coulsq && ((mi != mol[j]) || mi == 0)) {  // note <=, PS.cpp:342
         const double rinv = rsqrt(rsq);
         const double ef_temp = (rinv * rinv + f_shift) * rinv * rj.q;
         ex += ef_temp * dx; ey += ef_temp * dy; ez += ef_temp * dz;
@@ -493,7 +504,12 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_static_field(const int *
       double dx, dy, dz;
       pair_del<ALLPAIRS>(box, ri.x, ri.y, ri.z, xj, yj, zj, dx, dy, dz);
       const double rsq = dx * dx + dy * dy + dz * dz;
-      if (valid && j != i && rsq <= cut_coulsq && !(e & POLAR_NL_SAMEMOL)) {  // note <=, PS.cpp:342
+      if (EW) {
+        if (valid && j != i && rsq <= cut_coulsq) {
+          const double ef_temp = ewald_b1(rsq, g_ewald, !(e & POLAR_NL_SAMEMOL)) * qj;
+          ex += ef_temp * dx; ey += ef_temp * dy; ez += ef_temp * dz;
+        }
+      } else if (valid && j != i && rsq <= cut_coulsq && !(e & POLAR_NL_SAMEMOL)) {  // note <=, PS.cpp:342
         const double rinv = rsqrt(rsq);
         const double ef_temp = (rinv * rinv + f_shift) * rinv * qj;
         ex += ef_temp * dx; ey += ef_temp * dy; ez += ef_temp * dz;
@@ -503,6 +519,7 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_static_field(const int *
   ex = wave_sum(ex); ey = wave_sum(ey); ez = wave_sum(ez);
   if (lane == 0) {
     ex *= e2s; ey *= e2s; ez *= e2s;
+    if (EW) { ex += erec[3 * i]; ey += erec[3 * i + 1]; ez += erec[3 * i + 2]; }
     ef[3 * i] = ex; ef[3 * i + 1] = ey; ef[3 * i + 2] = ez;
     if (!use_previous) {  // mu = gamma * alpha * E
       const double a = ri.a;
@@ -514,12 +531,41 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_static_field(const int *
   }
 }
 
+template <bool ALLPAIRS>
+static __global__ __launch_bounds__(POLAR_BLOCK) void k_static_field(const int *__restrict__ rows, int nrows, int nlocal,
+                                                              const AtomRec *__restrict__ rec,
+                                                              const int *__restrict__ mol, Box box,
+                                                              RowList nl,
+                                                              const int *__restrict__ nl_j, double cut_coulsq,
+                                                              double e2s, double gamma, int use_previous,
+                                                              double *__restrict__ ef, AtomRec *__restrict__ rec0,
+                                                              AtomRec *__restrict__ rec1, const double4 *__restrict__ xq_s) {
+  static_field_body<ALLPAIRS, false>(rows, nrows, nlocal, rec, mol, box, nl, nl_j, cut_coulsq, e2s, gamma, use_previous, ef, rec0, rec1,
+                                     xq_s, 0.0, nullptr);
+}
+template <bool ALLPAIRS>
+static __global__ __launch_bounds__(POLAR_BLOCK) void k_ew_static_field(const int *__restrict__ rows, int nrows, int nlocal,
+                                                                 const AtomRec *__restrict__ rec,
+                                                                 const int *__restrict__ mol, Box box,
+                                                                 RowList nl,
+                                                                 const int *__restrict__ nl_j, double cut_coulsq,
+                                                                 double e2s, double gamma, int use_previous,
+                                                                 double *__restrict__ ef, AtomRec *__restrict__ rec0,
+                                                                 AtomRec *__restrict__ rec1, const double4 *__restrict__ xq_s,
+                                                                 double g_ewald, const double *__restrict__ erec) {
+  static_field_body<ALLPAIRS, true>(rows, nrows, nlocal, rec, mol, box, nl, nl_j, cut_coulsq, e2s, gamma, use_previous, ef, rec0, rec1,
+                                    xq_s, g_ewald, erec);
+}
+
 // ------------------------------------------------------------------------------------------
 // a8  polarization forces and energies, PS.cpp:406-641, evaluated per row (force on i from every j).
 // The pair force is antisymmetric, so summing rows reproduces the reference's i<j scatter;
 // pair energies are counted from both rows and halved.
-template <bool ALLPAIRS, int DAMP, bool EFLAG, bool VPAIR>
-static __global__ __launch_bounds__(POLAR_BLOCK) void k_polar_force(const int *__restrict__ rows, int nrows, const int *__restrict__ perm,
+// EW (`polar_ewald`): the charge-dipole part is the gradient of the real-space Ewald field (ewald_b12: erfc-damped tensors
+// over the kept pairs, the erf correction over the excluded ones, r <= cut_coul); u_ef is left to k_ew_force (-sum mu.E).
+// (one body, two kernels, as for the static field: k_ew_polar_force is the EW form)
+template <bool ALLPAIRS, int DAMP, bool EFLAG, bool VPAIR, bool EW>
+static __device__ __forceinline__ void polar_force_body(const int *__restrict__ rows, int nrows, const int *__restrict__ perm,
                                                              int nlocal, const Scal *scal_in,
                                                              const AtomRec *__restrict__ recA,
                                                              const AtomRec *__restrict__ recB,
@@ -529,7 +575,7 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_polar_force(const int *_
                                                              double ddcutsq, double pd, double e2s,
                                                              double *__restrict__ f, double *__restrict__ slots,
                                                              double *__restrict__ vatom, int vglobal, ExpCoef K,
-                                                             double *__restrict__ dbg6) {
+                                                             double *__restrict__ dbg6, double g_ewald) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * POLAR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (row >= nrows) return;
@@ -562,7 +608,20 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_polar_force(const int *_
     const double r = rsq * rinv;
     const double r3inv = r2inv * rinv;
     double px = 0, py = 0, pz = 0;
-    if (rsq < cut_coulsq && molok) {  // note <, PS.cpp:454
+    if (EW) {
+      if (rsq <= cut_coulsq) {  // F_i = e2s [q_j (B1 mu_i - B2 (mu_i.d) d) - q_i (B1 mu_j - B2 (mu_j.d) d)]
+        double b1, b2;
+        ewald_b12(rsq, g_ewald, molok, b1, b2);
+        if (ri.a != 0.0 && rj.q != 0.0) {
+          const double c = rj.q * e2s, pr = (ri.mx * dx + ri.my * dy + ri.mz * dz) * b2;
+          px += c * (b1 * ri.mx - pr * dx); py += c * (b1 * ri.my - pr * dy); pz += c * (b1 * ri.mz - pr * dz);
+        }
+        if (rj.a != 0.0 && ri.q != 0.0) {
+          const double c = ri.q * e2s, pr = (rj.mx * dx + rj.my * dy + rj.mz * dz) * b2;
+          px -= c * (b1 * rj.mx - pr * dx); py -= c * (b1 * rj.my - pr * dy); pz -= c * (b1 * rj.mz - pr * dz);
+        }
+      }
+    } else if (rsq < cut_coulsq && molok) {  // note <, PS.cpp:454
       // shifted-force charge-dipole tensor G_pq = delta_pq (r^-2 + f_shift) r^2 ... written as the
       // reference does: M_pp = (-2 p^2 + q^2 + s^2) r2inv + f_shift (q^2 + s^2), M_pq = -pq (3 r2inv + f_shift)
       const double mxx = (-2.0 * xsq + ysq + zsq) * r2inv + f_shift * (ysq + zsq);
@@ -652,6 +711,23 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_polar_force(const int *_
       }
     }
   }
+}
+
+template <bool ALLPAIRS, int DAMP, bool EFLAG, bool VPAIR>
+static __global__ __launch_bounds__(POLAR_BLOCK) void k_polar_force(
+    const int *__restrict__ rows, int nrows, const int *__restrict__ perm, int nlocal, const Scal *scal_in,
+    const AtomRec *__restrict__ recA, const AtomRec *__restrict__ recB, const int *__restrict__ mol, Box box, RowList nl,
+    const int *__restrict__ nl_j, double cut_coulsq, double ddcutsq, double pd, double e2s, double *__restrict__ f,
+    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6) {
+  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, false>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, 0.0);
+}
+template <bool ALLPAIRS, int DAMP, bool EFLAG, bool VPAIR>
+static __global__ __launch_bounds__(POLAR_BLOCK) void k_ew_polar_force(
+    const int *__restrict__ rows, int nrows, const int *__restrict__ perm, int nlocal, const Scal *scal_in,
+    const AtomRec *__restrict__ recA, const AtomRec *__restrict__ recB, const int *__restrict__ mol, Box box, RowList nl,
+    const int *__restrict__ nl_j, double cut_coulsq, double ddcutsq, double pd, double e2s, double *__restrict__ f,
+    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6, double g_ewald) {
+  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, true>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, g_ewald);
 }
 
 static __global__ void k_add_into(long long n, const double *__restrict__ src, double *__restrict__ dst) {

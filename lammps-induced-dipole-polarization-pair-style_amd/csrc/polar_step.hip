@@ -408,14 +408,149 @@ void launch_force(polar_handle *h, int eflag, int vglobal, double *vatom, double
     HIPCHECK(hipMemsetAsync(h->d_dbgf.p, 0, 8 * sizeof(double), h->stream));
     dbg6 = h->d_dbgf.p;
   }
+  const bool ew = ewald_on(h);
+  const double g = h->P.g_ewald;
 #define LF(E, V)                                                                                                    \
-  k_polar_force<AP, DAMP, E, V><<<grid, block, 0, h->stream>>>(own_rows(h), own_n(h), h->sorted ? h->d_perm.p : nullptr, h->nlocal, h->d_scal.p, h->d_rec0.p, h->d_rec1.p,  \
+  if (ew) k_ew_polar_force<AP, DAMP, E, V><<<grid, block, 0, h->stream>>>(own_rows(h), own_n(h), h->sorted ? h->d_perm.p : nullptr, h->nlocal, h->d_scal.p, h->d_rec0.p, h->d_rec1.p,  \
+                                                               h->d_mol_s.p, h->box, RowList{h->d_nl_cnt.p, h->nl_pitch}, h->d_nl_j.p,  \
+                                                               ccs, dds, st.polar_damp, e2s, fdst, h->d_slots.p, vatom, vglobal, make_expcoef(),  \
+                                                               dbg6, g);                                        \
+  else k_polar_force<AP, DAMP, E, V><<<grid, block, 0, h->stream>>>(own_rows(h), own_n(h), h->sorted ? h->d_perm.p : nullptr, h->nlocal, h->d_scal.p, h->d_rec0.p, h->d_rec1.p,  \
                                                                h->d_mol_s.p, h->box, RowList{h->d_nl_cnt.p, h->nl_pitch}, h->d_nl_j.p,  \
                                                                ccs, dds, st.polar_damp, e2s, fdst, h->d_slots.p, vatom, vglobal, make_expcoef(),  \
                                                                dbg6)
-  if (eflag) { if (vpair) LF(true, true); else LF(true, false); }
-  else       { if (vpair) LF(false, true); else LF(false, false); }
+  if (eflag) { if (vpair) { LF(true, true); } else { LF(true, false); } }
+  else       { if (vpair) { LF(false, true); } else { LF(false, false); } }
 #undef LF
+}
+
+// ---- `polar_ewald <accuracy>`: the reciprocal-space half of the Ewald static field and of its forces (polar_ewald.hpp) ----
+// LDS of k_ew_sfac: per staged atom, three power tables of nm + 1 entries and three weights; up to 32 atoms in 48 KB
+size_t ewald_lds_per_atom(int nm) { return 3 * (size_t)(nm + 1) * sizeof(double2) + 3 * sizeof(double); }
+int ewald_tile(int nm) { return (int)std::max<size_t>(1, std::min<size_t>(32, (48 * 1024) / ewald_lds_per_atom(nm))); }
+
+// the half-space k-vectors with |k| <= k_cut, in (h, k, l) order, grouped in rows of consecutive l; rebuilt when the box,
+// g_ewald or the accuracy changed
+void ewald_kvectors(polar_handle *h) {
+  const Box &b = h->box;
+  const double g = h->P.g_ewald, acc = h->ph.st.polar_ewald;
+  std::vector<double> key = {b.prd[0], b.prd[1], b.prd[2], b.xy, b.xz, b.yz, g, acc};
+  if (key == h->ew_key) return;
+  const double lx = b.prd[0], ly = b.prd[1], lz = b.prd[2], xy = b.xy, xz = b.xz, yz = b.yz;
+  // H = [a b c] = [[lx, xy, xz], [0, ly, yz], [0, 0, lz]];  s = H^-1 r;  k = 2 pi H^-T n
+  const double i00 = 1.0 / lx, i01 = -xy / (lx * ly), i02 = (xy * yz - ly * xz) / (lx * ly * lz), i11 = 1.0 / ly,
+               i12 = -yz / (ly * lz), i22 = 1.0 / lz;
+  const double vol = lx * ly * lz, twopi = 2.0 * M_PI;
+  const double kcut = 2.0 * g * std::sqrt(-std::log(acc)), kcut2 = kcut * kcut;
+  // |n_a| <= k_cut |lattice vector a| / 2 pi
+  const int hm = (int)std::floor(kcut * lx / twopi), km = (int)std::floor(kcut * std::sqrt(xy * xy + ly * ly) / twopi),
+            lm = (int)std::floor(kcut * std::sqrt(xz * xz + yz * yz + lz * lz) / twopi);
+  std::vector<double4> kv;
+  std::vector<int4> hkl, rows;
+  for (int ih = 0; ih <= hm; ih++)
+    for (int ik = (ih == 0 ? 0 : -km); ik <= km; ik++) {
+      int row = -1;
+      for (int il = (ih == 0 && ik == 0 ? 1 : -lm); il <= lm; il++) {
+        const double kx = twopi * (ih * i00), ky = twopi * (ih * i01 + ik * i11), kz = twopi * (ih * i02 + ik * i12 + il * i22);
+        const double k2 = kx * kx + ky * ky + kz * kz;
+        if (k2 > kcut2 || k2 == 0.0) continue;
+        if (row < 0) { row = (int)rows.size(); rows.push_back(make_int4(ih, ik, il, (int)kv.size())); }
+        kv.push_back(make_double4(kx, ky, kz, 8.0 * M_PI / vol * std::exp(-k2 / (4.0 * g * g)) / k2));
+        hkl.push_back(make_int4(ih, ik, il, 0));
+      }
+    }
+  h->ew_nk = (int)kv.size();
+  h->ew_nrow = (int)rows.size();
+  rows.push_back(make_int4(0, 0, 0, h->ew_nk));
+  h->ew_nm = std::max(hm, std::max(km, lm));
+  h->ew_cell[0] = i00; h->ew_cell[1] = i01; h->ew_cell[2] = i02; h->ew_cell[3] = i11; h->ew_cell[4] = i12; h->ew_cell[5] = i22;
+  h->d_ew_kv.ensure(kv.size() + 1); h->d_ew_hkl.ensure(hkl.size() + 1); h->d_ew_rows.ensure(rows.size());
+  h->d_ew_s.ensure(kv.size() + 1); h->d_ew_m.ensure(kv.size() + 1);
+  if (!kv.empty()) {
+    HIPCHECK(hipMemcpyAsync(h->d_ew_kv.p, kv.data(), kv.size() * sizeof(double4), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->d_ew_hkl.p, hkl.data(), hkl.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+  }
+  HIPCHECK(hipMemcpyAsync(h->d_ew_rows.p, rows.data(), rows.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));  // (the host vectors go out of scope)
+  h->ew_key = key;
+}
+
+// what the keyword is not offered with (POLAR_ERR_UNSUPPORTED); thrown before the step touches anything
+void ewald_check(polar_handle *h, int vflag) {
+  const polar_settings &st = h->ph.st;
+  if (sharded(h)) throw Unsupported("polar_ewald needs one handle over all atoms: on a row-sharded handle the structure factors would need an all-reduce across the ranks");
+  if (st.rccl_halo) throw Unsupported("polar_ewald is not offered with rccl_halo yes: the structure factors would need an all-reduce across the ranks");
+  if (!(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2])) throw Unsupported("polar_ewald needs a box periodic in x, y and z");
+  if (vflag & 4) throw Unsupported("polar_ewald offers no per-atom virial (vflag & 4): the reciprocal-space virial has no pairwise definition");
+  if (!(h->P.g_ewald > 0.0)) throw InputError("polar_ewald needs g_ewald > 0 (polar_pair_init / polar_set_coul)");
+  ewald_kvectors(h);   // (host work and a synchronous upload, when the box, g_ewald or the accuracy changed)
+  if ((size_t)ewald_tile(h->ew_nm) * ewald_lds_per_atom(h->ew_nm) > 64 * 1024)
+    throw Unsupported("polar_ewald: the k-vector range per box axis is too large for the structure-factor kernel (raise the accuracy value or g_ewald)");
+}
+
+// cut_coul beyond half the smallest distance between lattice planes: a second image of a partner can lie within cut_coul
+bool ewald_short_box(const polar_handle *h) {
+  const Box &b = h->box;
+  const double lx = b.prd[0], ly = b.prd[1], lz = b.prd[2], xy = b.xy, xz = b.xz, yz = b.yz;
+  const double vol = lx * ly * lz;
+  // plane spacings V / |b x c|, V / |c x a|, V / |a x b| of a = (lx,0,0), b = (xy,ly,0), c = (xz,yz,lz)
+  const double bc[3] = {ly * lz, -xy * lz, xy * yz - ly * xz}, ca[3] = {0.0, lx * lz, -lx * yz}, ab[3] = {0.0, 0.0, lx * ly};
+  auto nrm = [](const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+  const double w = std::min(vol / nrm(bc), std::min(vol / nrm(ca), vol / nrm(ab)));
+  return h->ph.st.cut_coul > 0.5 * w;
+}
+
+EwCell ew_cell(const polar_handle *h) {
+  const double *c = h->ew_cell;
+  return EwCell{c[0], c[1], c[2], c[3], c[4], c[5]};
+}
+
+// S(k) (mu = false) or M(k) (mu = true) of the n atoms of the s-space records -> out[nk]
+void ewald_sfac(polar_handle *h, bool mu, double2 *out) {
+  const int n = h->nlocal, nk = h->ew_nk, nm = h->ew_nm;
+  if (nk == 0) return;
+  const int tile = ewald_tile(nm);
+  const size_t lds = (size_t)tile * ewald_lds_per_atom(nm);
+  const int kb = nblk(nk, 256);
+  int nchunk = std::max(1, std::min(nblk(std::max(n, 1), tile), nblk(4096, kb)));
+  const int chunk = std::max(1, nblk(std::max(n, 1), nchunk));
+  nchunk = nblk(std::max(n, 1), chunk);
+  h->d_ew_part.ensure((size_t)nchunk * nk);
+  dim3 grid(kb, nchunk);
+  if (mu) k_ew_sfac<true><<<grid, 256, lds, h->stream>>>(nk, h->d_ew_hkl.p, h->d_ew_kv.p, n, chunk, tile, nm, ew_cell(h), h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_ew_part.p);
+  else    k_ew_sfac<false><<<grid, 256, lds, h->stream>>>(nk, h->d_ew_hkl.p, h->d_ew_kv.p, n, chunk, tile, nm, ew_cell(h), nullptr, h->d_rec0.p, h->d_rec1.p, h->d_ew_part.p);
+  k_ew_fold<<<kb, 256, 0, h->stream>>>(nk, nchunk, h->d_ew_part.p, out);
+}
+
+// before the static-field kernel: S(k), then the reciprocal field of every atom into d_ew_erec (s space)
+void ewald_field(polar_handle *h) {
+  const int n = h->nlocal;
+  HIPCHECK(hipEventRecord(h->ev_ks[0], h->stream));   // (the k-vector set is current: ewald_check)
+  h->d_ew_erec.ensure(3 * (size_t)n + 3);
+  ewald_sfac(h, false, h->d_ew_s.p);
+  if (n > 0) {
+    if (h->ew_nk > 0)
+      k_ew_field<<<nblk(n, 256), 256, 0, h->stream>>>(n, h->ew_nrow, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, ew_cell(h), std::sqrt(h->P.qqrd2e), h->d_rec0.p, h->d_ew_erec.p);
+    else HIPCHECK(hipMemsetAsync(h->d_ew_erec.p, 0, 3 * (size_t)n * sizeof(double), h->stream));
+  }
+  HIPCHECK(hipEventRecord(h->ev_ks[1], h->stream));
+}
+
+// after the real-space forces (and the fdotr virial, which must not see these forces: the reciprocal virial has its own
+// formula): M(k), the reciprocal forces into d_f, and [u_ef, virial[6]] into d_ew_out
+void ewald_forces(polar_handle *h) {
+  const int n = h->nlocal, nk = h->ew_nk;
+  hipStream_t s = h->stream;
+  HIPCHECK(hipEventRecord(h->ev_ks[2], s));
+  ewald_sfac(h, true, h->d_ew_m.p);
+  const int nba = nblk(std::max(n, 1), 256), nbk = nk > 0 ? nblk(nk, 256) : 0;
+  h->d_ew_vpart.ensure(8 * (size_t)(nba + nbk)); h->d_ew_out.ensure(8);
+  const double e2s = std::sqrt(h->P.qqrd2e), g = h->P.g_ewald;
+  k_ew_force<<<nba, 256, 0, s>>>(n, nk > 0 ? h->ew_nrow : 0, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_ew_m.p, ew_cell(h), e2s, h->d_scal.p,
+                                 h->d_rec0.p, h->d_rec1.p, h->sorted ? h->d_perm.p : nullptr, h->d_ef_s.p, h->d_ew_erec.p, h->d_f.p, h->d_ew_vpart.p);
+  if (nbk) k_ew_kvirial<<<nbk, 256, 0, s>>>(nk, h->d_ew_kv.p, h->d_ew_s.p, h->d_ew_m.p, e2s, 1.0 / (4.0 * g * g), h->d_ew_vpart.p + 8 * (size_t)nba);
+  k_ew_finish<<<1, 256, 0, s>>>(nba + nbk, h->d_ew_vpart.p, h->d_ew_out.p);
+  HIPCHECK(hipEventRecord(h->ev_ks[3], s));
 }
 
 void read_scal(polar_handle *h) {
@@ -639,9 +774,13 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
   if (ap && own_n(h) != n) throw InputError("row sharding needs dd_cutoff > 0 (exact all-pairs mode runs as replicas only)");
   if (!ap && h->box.triclinic && !(h->sweep_kernel == 4 || (h->sweep_kernel == 2 && h->lp_depth == 0)))
     throw InputError("dd_cutoff (list) mode in a triclinic box needs the row sweep (k_field_lp) or, in the lab build, the tile sweep");
+  if (ewald_on(h)) ewald_check(h, vflag);
   const int vmode = vflag % 4;
   hipStream_t s = h->stream;
   h->warn.clear();
+  if (ewald_on(h) && ewald_short_box(h))
+    h->warn = "polar_ewald: cut_coul exceeds half a box width, and the real-space sum takes the minimum image only: the field is "
+              "the Ewald field only where erfc(g_ewald * half the box width) is negligible";
   h->ntrace = 0;
   h->step_eflag = eflag; h->step_vflag = vflag;
 
@@ -804,7 +943,12 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
   {  // a4 + a5
     dim3 grid(nblk(own_n(h), POLAR_ROWS_PER_BLOCK)), block(POLAR_BLOCK);
     const double ccs = st.cut_coul * st.cut_coul, e2s = std::sqrt(h->P.qqrd2e);
-    if (ap) k_static_field<true><<<grid, block, 0, s>>>(nullptr, n, n, h->d_rec0.p, h->d_mol_s.p, h->box, RowList{nullptr, 0}, nullptr, ccs, e2s, st.polar_gamma, st.use_previous, h->d_ef_s.p, h->d_rec0.p, h->d_rec1.p, nullptr);
+    if (ewald_on(h)) {  // `polar_ewald`: reciprocal field first, then the real-space kernel adds it in before the initial guess
+      ewald_field(h);
+      const double g = h->P.g_ewald;
+      if (ap) k_ew_static_field<true><<<grid, block, 0, s>>>(nullptr, n, n, h->d_rec0.p, h->d_mol_s.p, h->box, RowList{nullptr, 0}, nullptr, ccs, e2s, st.polar_gamma, st.use_previous, h->d_ef_s.p, h->d_rec0.p, h->d_rec1.p, nullptr, g, h->d_ew_erec.p);
+      else    k_ew_static_field<false><<<grid, block, 0, s>>>(own_rows(h), own_n(h), n, h->d_rec0.p, h->d_mol_s.p, h->box, RowList{h->d_nl_cnt.p, h->nl_pitch}, h->d_nl_j.p, ccs, e2s, st.polar_gamma, st.use_previous, h->d_ef_s.p, h->d_rec0.p, h->d_rec1.p, h->static_xq ? h->d_xq_s.p : nullptr, g, h->d_ew_erec.p);
+    } else if (ap) k_static_field<true><<<grid, block, 0, s>>>(nullptr, n, n, h->d_rec0.p, h->d_mol_s.p, h->box, RowList{nullptr, 0}, nullptr, ccs, e2s, st.polar_gamma, st.use_previous, h->d_ef_s.p, h->d_rec0.p, h->d_rec1.p, nullptr);
     else    k_static_field<false><<<grid, block, 0, s>>>(own_rows(h), own_n(h), n, h->d_rec0.p, h->d_mol_s.p, h->box, RowList{h->d_nl_cnt.p, h->nl_pitch}, h->d_nl_j.p, ccs, e2s, st.polar_gamma, st.use_previous, h->d_ef_s.p, h->d_rec0.p, h->d_rec1.p, h->static_xq ? h->d_xq_s.p : nullptr);
   }
   // tile sweep: the solve works on 48-byte sweep records {position, dipole}; the initial dipoles are in the AtomRecs now
@@ -861,6 +1005,7 @@ int phase_finish(polar_handle *h, polar_result *out) {
     k_virial_fdotr<<<std::min(1024, nblk(n, 256)), 256, 0, s>>>(n, h->d_x.p, h->d_fpol.p, h->d_slots.p);
     k_add_into<<<nblk(3 * (long long)n, 256), 256, 0, s>>>(3 * (long long)n, h->d_fpol.p, h->d_f.p);
   } else if (vmode == 2) k_virial_fdotr<<<std::min(1024, nblk(nall, 256)), 256, 0, s>>>(nall, h->d_x.p, h->d_f.p, h->d_slots.p);  // a10
+  if (ewald_on(h)) ewald_forces(h);  // (after the fdotr virial: the reciprocal forces are not pair forces)
   k_fold_scal<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, 0);
   HIPCHECK(hipEventRecord(h->ev[6], s));
   if (h->early_mu && h->user_mu && n > 0) {  // the force kernel is still running: the dipoles and the field, on the host by now, go into the caller's arrays meanwhile
@@ -881,6 +1026,18 @@ int phase_finish(polar_handle *h, polar_result *out) {
   out->u_self = sc.u_self; out->u_ef = sc.u_ef; out->u_dd = sc.u_dd;
   out->eng_pol = sc.u_self + sc.u_ef + sc.u_dd;  // PS.cpp:632 (all zero when eflag == 0)
   for (int k = 0; k < 6; k++) out->virial[k] = sc.virial[k];
+  if (ewald_on(h)) {  // u_ef = -sum mu . E_static over the whole Ewald field; the reciprocal virial by its k-space formula
+    double ew[7];
+    HIPCHECK(hipMemcpyAsync(ew, h->d_ew_out.p, sizeof(ew), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    if (eflag) { out->u_ef = ew[0]; out->eng_pol = sc.u_self + ew[0] + sc.u_dd; }
+    if (vmode) for (int k = 0; k < 6; k++) out->virial[k] += ew[1 + k];
+    float a = 0.f, b = 0.f;
+    HIPCHECK(hipEventElapsedTime(&a, h->ev_ks[0], h->ev_ks[1]));
+    HIPCHECK(hipEventElapsedTime(&b, h->ev_ks[2], h->ev_ks[3]));
+    out->ms_kspace = (double)a + (double)b;
+    out->nkvec = h->ew_nk;
+  }
   long long rb = (long long)sc.rmin_bits;
   memcpy(&out->rmin, &rb, sizeof(double));
   out->rms_dmu = std::sqrt(std::max(0.0, sc.last_change));

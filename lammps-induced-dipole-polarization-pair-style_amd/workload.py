@@ -350,6 +350,7 @@ class PolarSettings:
     polar_sor: float = 1.0  # extension: over-relaxation factor of the list-mode Gauss-Seidel update (1 = reference)
     rccl_halo: int = 0      # extension: the LAMMPS shim's multi-rank sweeps run through the library's RCCL driver
     polar_accel: int = 0    # extension: Anderson mixing of this depth on the list-mode Gauss-Seidel sweep map (0 = off)
+    polar_ewald: float = 0.0  # extension: Ewald-summed static field, reciprocal cutoff from exp(-k^2/4g^2) <= this (0 = off)
 
 
 @dataclass
@@ -765,6 +766,10 @@ def parse_pair_style_args(args, base=None):
         elif k == "polar_accel":  # extension keyword (not in the reference)
             st.polar_accel = int(v)
             if not 0 <= st.polar_accel <= 8:
+                raise ValueError("Illegal pair_style command")
+        elif k == "polar_ewald":  # extension keyword (not in the reference)
+            st.polar_ewald = float(v)
+            if not 0.0 <= st.polar_ewald < 1.0:
                 raise ValueError("Illegal pair_style command")
         elif k == "polar_sor":  # extension keyword (not in the reference)
             st.polar_sor = float(v)

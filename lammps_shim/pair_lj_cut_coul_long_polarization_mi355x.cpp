@@ -591,6 +591,10 @@ void PairLJCutCoulLongPolarizationMI355X::init_style()
       if (!neighbor->ex_mol_intra[k])
         error->all(FLERR,"Pair style lj/cut/coul/long/polarization device_neigh supports only neigh_modify exclude molecule/intra all");
   }
+  // extension keyword `polar_ewald`: the library adds reciprocal-space charge-dipole forces to atom->f, whose virial is not
+  // sum x_i F_i but a k-space formula -- the base class must not form the fdotr virial; a global virial request then reaches
+  // the library as pairwise (vflag_global 1, or 2 with device_neigh), and res.virial holds the reciprocal part as well
+  if (pst.polar_ewald > 0.0) no_virial_fdotr_compute = 1;
   if (force->kspace == NULL) error->all(FLERR,"Pair style requires a KSpace style");
 
   // pair_modify state lives in the Pair base class; mirror it into the library, then let it build
