@@ -353,6 +353,40 @@ __device__ __forceinline__ double exp_neg(double x, const ExpCoef &K) {
   for (int k = 12; k >= 0; k--) p = fma(p, r, K.c[k]);
   return ldexp(p, (int)n);
 }
+// 1/sqrt(x), x > 0 finite: v_rsq_f64 (about 2^-23 relative) and one second-order (Newton) correction: 2^-45 = 3e-14
+// relative, four instructions (the third-order form bought 2^-69 for a fifth: the sweep is bound by its instruction count)
+__device__ __forceinline__ double rsqrt_pos(double x) {
+  const double y = __builtin_amdgcn_rsq(x);
+  const double e = fma(-(x * y), y, 1.0);
+  return fma(y * e, 0.5, y);
+}
+// the third-order form: y (1 + e/2 + 3 e^2/8), e = 1 - x y^2 <= 2^-22: 2^-69 before the last rounding, i.e. correct to an
+// ulp, five instructions.  The force kernel takes this one: its energies are sums of one-signed terms (the second-order
+// form's error is one-signed too, and eng_pol is compared to 1e-12).
+__device__ __forceinline__ double rsqrt_pos3(double x) {
+  const double y = __builtin_amdgcn_rsq(x);
+  const double e = fma(-(x * y), y, 1.0);
+  return fma(y * e, fma(e, 0.375, 0.5), y);
+}
+// exp(x), -700 <= x <= 0 after the clamp: round-to-nearest of x*log2(e) through the 1.5*2^52 shift (the integer lands
+// in the low word), Cody-Waite remainder, Taylor polynomial of degree DEG (|r| <= ln2/2: truncation 2.2e-13 relative at
+// degree 10, the sweep's -- the damping term e^(-ar) p(ar) it feeds is at most 0.3 of the tensor scalar, three orders
+// inside the parity tolerance -- and 1.7e-16 at degree 12, the force kernel's), and the power of two added straight into
+// the exponent field (the result stays normal: n >= -1010).
+template <int DEG = 10>
+__device__ __forceinline__ double exp_neg_fast(double x, const ExpCoef &K) {
+  static_assert(DEG >= 1 && DEG <= 13, "ExpCoef holds 1/k! up to k = 13");
+  x = fmax(x, -700.0);
+  const double shift = 6755399441055744.0;
+  const double ns = fma(x, K.log2e, shift);
+  const double n = ns - shift;
+  double r = fma(-n, K.ln2hi, x);
+  r = fma(-n, K.ln2lo, r);
+  double p = K.c[DEG];
+#pragma unroll
+  for (int k = DEG - 1; k >= 0; k--) p = fma(p, r, K.c[k]);
+  return __hiloint2double(__double2hiint(p) + (__double2loint(ns) << 20), __double2loint(p));
+}
 
 // Dipole field tensor scalars of build_dipole_field_matrix (PS.cpp:1284-1306):
 //   T_pq = delta_pq * s3 - d_p d_q * s5,  s3 = damp1 / r^3,  s5 = 3 damp2 / r^5

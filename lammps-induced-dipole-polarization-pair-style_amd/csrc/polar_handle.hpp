@@ -251,6 +251,9 @@ struct polar_handle {
   bool sym_typed = false, dev_typed = false;
   int static_xq = 1;             // the static-field rows gather 32-byte {x, y, z, q} records instead of whole AtomRecs (POLAR_STATIC_XQ=0)
   int pol_first = 1;             // polarizable atoms first inside a cell (POLAR_POL_FIRST=0: arrival order)
+#ifdef POLAR_LAB
+  int force_literal = 0;         // the polarization force kernels run the term-by-term pair arithmetic of lab/force_pair_literal.hpp (POLAR_FORCE_LITERAL=1)
+#endif
   int part_k = 0, part_n = 1;    // polar_step_sweep_part: which share of the colour phases the next sweep_once runs
   int lp_wg_per_cu = 0;          // lab (POLAR_LP_WG_PER_CU): workgroups of k_field_lp resident per CU, capped through the LDS size
   int lp_quad_major = 1;         // slot order of the lp index stream (lp_slot), POLAR_LP_QM=0: lane = entry

@@ -4,6 +4,15 @@
 #pragma once
 
 #include "polar_common.hpp"
+#include "polar_force_pair.hpp"
+#ifdef POLAR_LAB
+#include "lab/force_pair_literal.hpp"   // the term-by-term pair arithmetic, the lab library's A/B partner (POLAR_FORCE_LITERAL=1)
+#define POLAR_LIT_PARAM , int literal
+#define POLAR_LIT_PASS , literal
+#else
+#define POLAR_LIT_PARAM
+#define POLAR_LIT_PASS
+#endif
 
 namespace polar {
 
@@ -557,6 +566,15 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_ew_static_field(const in
                                     xq_s, g_ewald, erec);
 }
 
+// the device form of polar_force_pair()'s math policy: Newton rsqrt, polynomial exp with its constants in scalar registers
+struct PairMath {
+  const ExpCoef &K;
+  double g_ewald;
+  __device__ __forceinline__ double rsqrt(double x) const { return rsqrt_pos3(x); }
+  __device__ __forceinline__ double exp_neg(double x) const { return exp_neg_fast<12>(x, K); }
+  __device__ __forceinline__ void ewald_b12(double rsq, bool kept, double &b1, double &b2) const { polar::ewald_b12(rsq, g_ewald, kept, b1, b2); }
+};
+
 // ------------------------------------------------------------------------------------------
 // a8  polarization forces and energies, PS.cpp:406-641, evaluated per row (force on i from every j).
 // The pair force is antisymmetric, so summing rows reproduces the reference's i<j scatter;
@@ -575,7 +593,7 @@ static __device__ __forceinline__ void polar_force_body(const int *__restrict__ 
                                                              double ddcutsq, double pd, double e2s,
                                                              double *__restrict__ f, double *__restrict__ slots,
                                                              double *__restrict__ vatom, int vglobal, ExpCoef K,
-                                                             double *__restrict__ dbg6, double g_ewald) {
+                                                             double *__restrict__ dbg6, double g_ewald POLAR_LIT_PARAM) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * POLAR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (row >= nrows) return;
@@ -583,104 +601,70 @@ static __device__ __forceinline__ void polar_force_body(const int *__restrict__ 
   const AtomRec *__restrict__ rec = __builtin_amdgcn_readfirstlane(scal_in->cur) ? recB : recA;  // scalar base
   const AtomRec ri = uniform_rec(rec[i]);  // row data is the same in every lane: scalar registers
   const int mi = mol[i];
-  const double f_shift = -1.0 / cut_coulsq;
+  const PairRow pri = make_pair_row(ri.mx, ri.my, ri.mz, ri.q, ri.a, e2s);   // wave-uniform: scalar registers
+  const PairCut cut{cut_coulsq, ddcutsq, -1.0 / cut_coulsq, pd};
+  const PairMath pm{K, g_ewald};
   double fx = 0, fy = 0, fz = 0, uef = 0, udd = 0;
   double v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0;
   // `debug yes` (PS.cpp:542-556, 612-626, 637-638): the row of the caller's atom 0 also keeps the dipole-dipole part of its force
   const bool isdbg = dbg6 && (perm ? perm[i] : i) == 0;   // wave-uniform
-  double ddx = 0, ddy = 0, ddz = 0;
+  double ddx = 0, ddy = 0, ddz = 0;   // every row sums its charge-dipole part (fx, fy, fz) and its dipole-dipole part apart
   long long beg = 0, end = nlocal;
   if (!ALLPAIRS) row_range(nl, i, beg, end);
-  // (the cooperative record fetch of k_static_field was tried here too: this kernel is bound by its FP64
-  //  arithmetic, not by the gathers, and got 7 % slower)
+  // list mode: a non-periodic direction takes no lattice vector off -- rint(d * 0) = 0 says so without a select per pair
+  // (bit-identical: the FMAs then add exact zeros).  Valid for min_image_rint alone, which reads periodic[] only to choose
+  // between rint(d * inv) and 0; min_image_del (exact mode) wraps by comparisons against prd / half and keeps the real box.
+  // pbox goes to pair_del() below and nowhere else.
+  Box pbox = box;
+  if (!ALLPAIRS) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) { pbox.inv[k] = box.periodic[k] ? box.inv[k] : 0.0; pbox.periodic[k] = 1; }
+  }
+  // Software prefetch, as in ljcoul_row: the index of trip t+2 and the record of trip t+1 travel while trip t is computed.
+  // Per trip the chain index -> record -> arithmetic is two dependent memory round trips; with the term-by-term arithmetic
+  // the kernel sat on its FP64 instructions AND on that chain at about the same level (either change
+  // alone moved nothing, the two together 0.70 -> 0.54 ms).  A lane past the end of its row asks for the row atom's own
+  // record: always a valid address.  (The cooperative record fetch of k_static_field, with the same prefetch: 0.53 ms at 4
+  // waves per SIMD and 20 KB of LDS -- no better, not kept.)
+  int e_n1 = i, e_n2 = i;
+  if (!ALLPAIRS) {
+    if (beg + lane < end) e_n1 = nl_j[beg + lane];
+    if (beg + lane + 64 < end) e_n2 = nl_j[beg + lane + 64];
+  }
+  AtomRec r_n1 = rec[e_n1 & POLAR_NL_MASK];
   for (long long p = beg + lane; p < end; p += 64) {
-    const int e = ALLPAIRS ? (int)p : nl_j[p];
+    const int e = ALLPAIRS ? (int)p : e_n1;
     const int j = ALLPAIRS ? e : (e & POLAR_NL_MASK);
+    const AtomRec rj = ALLPAIRS ? rec[j] : r_n1;
+    if (!ALLPAIRS) {
+      e_n1 = e_n2;
+      r_n1 = *reinterpret_cast<const AtomRec *>(reinterpret_cast<const char *>(rec) + ((unsigned)(e_n1 & POLAR_NL_MASK) << 6));
+      e_n2 = p + 128 < end ? nl_j[p + 128] : i;
+    }
     if (j == i) continue;
-    const AtomRec rj = *reinterpret_cast<const AtomRec *>(reinterpret_cast<const char *>(rec) + ((unsigned)j << 6));
     const bool molok = ALLPAIRS ? ((mi != mol[j]) || mi == 0) : !(e & POLAR_NL_SAMEMOL);
     double dx, dy, dz;
-    pair_del<ALLPAIRS>(box, ri.x, ri.y, ri.z, rj.x, rj.y, rj.z, dx, dy, dz);
-    const double xsq = dx * dx, ysq = dy * dy, zsq = dz * dz;
-    const double rsq = xsq + ysq + zsq;
-    const double rinv = rsqrt(rsq);
-    const double r2inv = rinv * rinv;
-    const double r = rsq * rinv;
-    const double r3inv = r2inv * rinv;
-    double px = 0, py = 0, pz = 0;
-    if (EW) {
-      if (rsq <= cut_coulsq) {  // F_i = e2s [q_j (B1 mu_i - B2 (mu_i.d) d) - q_i (B1 mu_j - B2 (mu_j.d) d)]
-        double b1, b2;
-        ewald_b12(rsq, g_ewald, molok, b1, b2);
-        if (ri.a != 0.0 && rj.q != 0.0) {
-          const double c = rj.q * e2s, pr = (ri.mx * dx + ri.my * dy + ri.mz * dz) * b2;
-          px += c * (b1 * ri.mx - pr * dx); py += c * (b1 * ri.my - pr * dy); pz += c * (b1 * ri.mz - pr * dz);
-        }
-        if (rj.a != 0.0 && ri.q != 0.0) {
-          const double c = ri.q * e2s, pr = (rj.mx * dx + rj.my * dy + rj.mz * dz) * b2;
-          px -= c * (b1 * rj.mx - pr * dx); py -= c * (b1 * rj.my - pr * dy); pz -= c * (b1 * rj.mz - pr * dz);
-        }
-      }
-    } else if (rsq < cut_coulsq && molok) {  // note <, PS.cpp:454
-      // shifted-force charge-dipole tensor G_pq = delta_pq (r^-2 + f_shift) r^2 ... written as the
-      // reference does: M_pp = (-2 p^2 + q^2 + s^2) r2inv + f_shift (q^2 + s^2), M_pq = -pq (3 r2inv + f_shift)
-      const double mxx = (-2.0 * xsq + ysq + zsq) * r2inv + f_shift * (ysq + zsq);
-      const double myy = (-2.0 * ysq + xsq + zsq) * r2inv + f_shift * (xsq + zsq);
-      const double mzz = (-2.0 * zsq + xsq + ysq) * r2inv + f_shift * (xsq + ysq);
-      const double k = -(3.0 * r2inv + f_shift);
-      const double mxy = k * dx * dy, mxz = k * dx * dz, myz = k * dy * dz;
-      const double ef_temp = (r2inv + f_shift) * rinv * e2s;
-      if (ri.a != 0.0 && rj.q != 0.0) {  // dipole on i, charge on j
-        const double cf = rj.q * e2s * r3inv;
-        px += cf * (ri.mx * mxx + ri.my * mxy + ri.mz * mxz);
-        py += cf * (ri.mx * mxy + ri.my * myy + ri.mz * myz);
-        pz += cf * (ri.mx * mxz + ri.my * myz + ri.mz * mzz);
-        if (EFLAG) uef -= ef_temp * rj.q * (ri.mx * dx + ri.my * dy + ri.mz * dz);
-      }
-      if (rj.a != 0.0 && ri.q != 0.0) {  // dipole on j, charge on i
-        const double cf = ri.q * e2s * r3inv;
-        px -= cf * (rj.mx * mxx + rj.my * mxy + rj.mz * mxz);
-        py -= cf * (rj.mx * mxy + rj.my * myy + rj.mz * myz);
-        pz -= cf * (rj.mx * mxz + rj.my * myz + rj.mz * mzz);
-        if (EFLAG) uef += ef_temp * ri.q * (rj.mx * dx + rj.my * dy + rj.mz * dz);
-      }
-    }
-    if (ri.a != 0.0 && rj.a != 0.0 && (ALLPAIRS || rsq < ddcutsq)) {  // dipole-dipole, PS.cpp:512-602
-      const double r5inv = r3inv * r2inv, r7inv = r5inv * r2inv;
-      const double pdotp = ri.mx * rj.mx + ri.my * rj.my + ri.mz * rj.mz;
-      const double pidotr = ri.mx * dx + ri.my * dy + ri.mz * dz;
-      const double pjdotr = rj.mx * dx + rj.my * dy + rj.mz * dz;
-      double pre_r, pre2, pre3;
-      if (DAMP == 0) {
-        const double t1 = exp_neg(-pd * r, K);
-        const double t2 = 1.0 + pd * r + 0.5 * pd * pd * r * r;
-        const double t3 = t2 + (1.0 / 6.0) * pd * pd * pd * r * r * r;
-        const double g2 = 1.0 - t1 * t2, g3 = 1.0 - t1 * t3;
-        const double pre1 = 3.0 * r5inv * pdotp * g2 - 15.0 * r7inv * pidotr * pjdotr * g3;
-        pre2 = 3.0 * r5inv * pjdotr * g3;
-        pre3 = 3.0 * r5inv * pidotr * g3;
-        const double pre4 = -pdotp * r3inv * (-t1 * (pd * rinv + pd * pd) + t1 * pd * t2 * rinv);
-        const double pre5 = 3.0 * pidotr * pjdotr * r5inv *
-                            (-t1 * (pd * rinv + pd * pd + 0.5 * r * pd * pd * pd) + t1 * pd * t3 * rinv);
-        pre_r = pre1 + pre4 + pre5;
-        if (EFLAG) udd += r3inv * pdotp * g2 - 3.0 * r5inv * pidotr * pjdotr * g3;
-      } else {
-        pre_r = 3.0 * r5inv * pdotp - 15.0 * r7inv * pidotr * pjdotr;
-        pre2 = 3.0 * r5inv * pjdotr;
-        pre3 = 3.0 * r5inv * pidotr;
-        if (EFLAG) udd += r3inv * pdotp - 3.0 * r5inv * pidotr * pjdotr;
-      }
-      const double qx = pre_r * dx + pre2 * ri.mx + pre3 * rj.mx, qy = pre_r * dy + pre2 * ri.my + pre3 * rj.my,
-                   qz = pre_r * dz + pre2 * ri.mz + pre3 * rj.mz;
-      px += qx; py += qy; pz += qz;
-      if (isdbg) { ddx += qx; ddy += qy; ddz += qz; }
-    }
-    fx += px; fy += py; fz += pz;
+    pair_del<ALLPAIRS>(pbox, ri.x, ri.y, ri.z, rj.x, rj.y, rj.z, dx, dy, dz);
+    double px, py, pz;
+#ifdef POLAR_LAB
+    if (literal) {   // wave-uniform
+      double qx, qy, qz, ue, ud;
+      polar_force_pair_literal<ALLPAIRS, DAMP, EFLAG, EW>(K, g_ewald, dx, dy, dz, ri, rj, molok, cut_coulsq, ddcutsq, pd, e2s, px, py, pz,
+                                                          qx, qy, qz, ue, ud);
+      fx += px; fy += py; fz += pz;          // (px, py, pz): the charge-dipole part
+      ddx += qx; ddy += qy; ddz += qz;
+      if (VPAIR) { px += qx; py += qy; pz += qz; }   // the tally below takes the pair's whole force
+      if (EFLAG) { uef += ue; udd += ud; }
+    } else
+#endif
+    polar_force_pair<ALLPAIRS, DAMP, EFLAG, EW, VPAIR>(pm, dx, dy, dz, pri, rj.mx, rj.my, rj.mz, rj.q, rj.a, molok, cut, fx, fy, fz,
+                                                       ddx, ddy, ddz, uef, udd, px, py, pz);
     if (VPAIR) {  // ev_tally_xyz, src/pair.cpp:1001-1075 (each pair seen from both rows -> 0.5)
       v0 += 0.5 * dx * px; v1 += 0.5 * dy * py; v2 += 0.5 * dz * pz;
       v3 += 0.5 * dx * py; v4 += 0.5 * dx * pz; v5 += 0.5 * dy * pz;
     }
   }
+  fx += ddx; fy += ddy; fz += ddz;
   fx = wave_sum(fx); fy = wave_sum(fy); fz = wave_sum(fz);
   if (lane == 0) {
     const int o = perm ? perm[i] : i;  // forces leave in LAMMPS' order
@@ -718,16 +702,16 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_polar_force(
     const int *__restrict__ rows, int nrows, const int *__restrict__ perm, int nlocal, const Scal *scal_in,
     const AtomRec *__restrict__ recA, const AtomRec *__restrict__ recB, const int *__restrict__ mol, Box box, RowList nl,
     const int *__restrict__ nl_j, double cut_coulsq, double ddcutsq, double pd, double e2s, double *__restrict__ f,
-    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6) {
-  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, false>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, 0.0);
+    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6 POLAR_LIT_PARAM) {
+  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, false>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, 0.0 POLAR_LIT_PASS);
 }
 template <bool ALLPAIRS, int DAMP, bool EFLAG, bool VPAIR>
 static __global__ __launch_bounds__(POLAR_BLOCK) void k_ew_polar_force(
     const int *__restrict__ rows, int nrows, const int *__restrict__ perm, int nlocal, const Scal *scal_in,
     const AtomRec *__restrict__ recA, const AtomRec *__restrict__ recB, const int *__restrict__ mol, Box box, RowList nl,
     const int *__restrict__ nl_j, double cut_coulsq, double ddcutsq, double pd, double e2s, double *__restrict__ f,
-    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6, double g_ewald) {
-  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, true>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, g_ewald);
+    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6, double g_ewald POLAR_LIT_PARAM) {
+  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, true>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, g_ewald POLAR_LIT_PASS);
 }
 
 static __global__ void k_add_into(long long n, const double *__restrict__ src, double *__restrict__ dst) {
@@ -753,3 +737,6 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_virial_fdotr(int nall, c
 }
 
 }  // namespace polar
+
+#undef POLAR_LIT_PARAM
+#undef POLAR_LIT_PASS

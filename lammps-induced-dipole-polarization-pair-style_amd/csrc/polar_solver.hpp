@@ -106,29 +106,7 @@ __device__ __forceinline__ void lp_gather(const char *srcc, int joff, unsigned p
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
                                    (__attribute__((address_space(3))) void *)(tile + R * 1024), 16, 0, 0);
 }
-// 1/sqrt(x), x > 0 finite: v_rsq_f64 (about 2^-23 relative) and one second-order (Newton) correction: 2^-45 = 3e-14
-// relative, four instructions (the third-order form bought 2^-69 for a fifth: the sweep is bound by its instruction count)
-__device__ __forceinline__ double rsqrt_pos(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  const double e = fma(-(x * y), y, 1.0);
-  return fma(y * e, 0.5, y);
-}
-// exp(x), -700 <= x <= 0 after the clamp: round-to-nearest of x*log2(e) through the 1.5*2^52 shift (the integer lands
-// in the low word), Cody-Waite remainder, Taylor polynomial of degree 10 (|r| <= ln2/2: truncation 2.2e-13 relative --
-// the damping term e^(-ar) p(ar) it feeds is at most 0.3 of the tensor scalar, three orders inside the parity tolerance),
-// and the power of two added straight into the exponent field (the result stays normal: n >= -1010).
-__device__ __forceinline__ double exp_neg_fast(double x, const ExpCoef &K) {
-  x = fmax(x, -700.0);
-  const double shift = 6755399441055744.0;
-  const double ns = fma(x, K.log2e, shift);
-  const double n = ns - shift;
-  double r = fma(-n, K.ln2hi, x);
-  r = fma(-n, K.ln2lo, r);
-  double p = K.c[10];
-#pragma unroll
-  for (int k = 9; k >= 0; k--) p = fma(p, r, K.c[k]);
-  return __hiloint2double(__double2hiint(p) + (__double2loint(ns) << 20), __double2loint(p));
-}
+// (rsqrt_pos and exp_neg_fast: polar_common.hpp -- the force kernel shares them)
 template <int DAMP>
 __device__ __forceinline__ void tensor_scalars_lp(double r2, double pd, const ExpCoef &K, double &s3, double &s5) {
   const double rinv = rsqrt_pos(r2);

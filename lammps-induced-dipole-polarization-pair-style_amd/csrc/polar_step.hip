@@ -410,18 +410,24 @@ void launch_force(polar_handle *h, int eflag, int vglobal, double *vatom, double
   }
   const bool ew = ewald_on(h);
   const double g = h->P.g_ewald;
+#ifdef POLAR_LAB
+#define POLAR_LIT_ARG , h->force_literal
+#else
+#define POLAR_LIT_ARG
+#endif
 #define LF(E, V)                                                                                                    \
   if (ew) k_ew_polar_force<AP, DAMP, E, V><<<grid, block, 0, h->stream>>>(own_rows(h), own_n(h), h->sorted ? h->d_perm.p : nullptr, h->nlocal, h->d_scal.p, h->d_rec0.p, h->d_rec1.p,  \
                                                                h->d_mol_s.p, h->box, RowList{h->d_nl_cnt.p, h->nl_pitch}, h->d_nl_j.p,  \
                                                                ccs, dds, st.polar_damp, e2s, fdst, h->d_slots.p, vatom, vglobal, make_expcoef(),  \
-                                                               dbg6, g);                                        \
+                                                               dbg6, g POLAR_LIT_ARG);                          \
   else k_polar_force<AP, DAMP, E, V><<<grid, block, 0, h->stream>>>(own_rows(h), own_n(h), h->sorted ? h->d_perm.p : nullptr, h->nlocal, h->d_scal.p, h->d_rec0.p, h->d_rec1.p,  \
                                                                h->d_mol_s.p, h->box, RowList{h->d_nl_cnt.p, h->nl_pitch}, h->d_nl_j.p,  \
                                                                ccs, dds, st.polar_damp, e2s, fdst, h->d_slots.p, vatom, vglobal, make_expcoef(),  \
-                                                               dbg6)
+                                                               dbg6 POLAR_LIT_ARG)
   if (eflag) { if (vpair) { LF(true, true); } else { LF(true, false); } }
   else       { if (vpair) { LF(false, true); } else { LF(false, false); } }
 #undef LF
+#undef POLAR_LIT_ARG
 }
 
 // ---- `polar_ewald <accuracy>`: the reciprocal-space half of the Ewald static field and of its forces (polar_ewald.hpp) ----
