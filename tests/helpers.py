@@ -23,6 +23,8 @@ def golden_refs(case=None):
     out = []
     for p in sorted(glob.glob(os.path.join(GOLD, "ref_*.npz"))):
         z = np.load(p)
+        if "info" not in z.files:   # ref_closest_image.npz: recorded images, not a pair-style run (tests/test_closest_image.py)
+            continue
         info = json.loads(str(z["info"]))
         if case is None or info["case"] == case:
             out.append((p, info))

@@ -130,7 +130,8 @@ def test_two_consecutive_steps_reuse_lists_and_colours(wl, pkg, oracle):
 def test_triclinic_box_exact_mode(wl, pkg, oracle):
     """Triclinic branch of Domain::closest_image (domain.cpp:1258-1305) in the all-pairs kernels.
     No LJ/coul list here (inum = 0, no ghosts): the polarization loops are the ones that use the
-    minimum image.  Checker = the oracle's restatement of the triclinic branch."""
+    minimum image.  Checker = the oracle, whose orc_closest_image is pinned bit for bit, triclinic branch included, by the
+    reference's compiled domain.cpp (tests/test_closest_image.py, tests/golden/ref_closest_image.npz)."""
     rng = np.random.default_rng(11)
     n, L = 90, 16.0
     s = _mini(wl, n=n, seed=11, L=L, cut=7.5)
@@ -153,8 +154,10 @@ def test_triclinic_box_exact_mode(wl, pkg, oracle):
         out, ref = _check(pkg, oracle, s2)
         assert out["iterations"] == ref["iterations"]
     # list mode in the tilted cell (cell grid in fractional coordinates, whole lattice vectors taken off c, b, a):
-    # against the oracle's list mode, whose pair list comes from closest_image's triclinic branch.  "Restated,
-    # unpinned": no reference log or golden exercises a tilted box.
+    # against the oracle's list mode, whose pair list comes from closest_image's triclinic branch.  That branch is pinned
+    # by the reference's compiled domain.cpp (tests/test_closest_image.py); the device functions are compared with the
+    # recorded images directly, and this cell's pair count with brute force, in tests/test_gpu_closest_image.py.  (With
+    # cut 7.5 in a 16 A cell no pair here reaches an image that is not the nearest one; the exact-mode tensor above does.)
     for extra in (["precision", "1e-13", "max_iterations", "200"],
                   ["polar_gs_ranked", "no", "fixed_iteration", "yes", "max_iterations", "5"]):
         s2.settings = wl.parse_pair_style_args(["8.0", "7.5", "damp_type", "exponential", "dd_cutoff", "7.5"] + extra)
