@@ -21,3 +21,4 @@
   if (const char *e = getenv("POLAR_QUAD_BLOCK")) { int v = atoi(e); if (v >= 64 && v <= 1024 && v % 64 == 0) h->quad_block = v; }
   if (const char *e = getenv("POLAR_FIELD_BLOCK")) { int v = atoi(e); if (v >= 64 && v <= 1024 && v % 64 == 0) h->field_block = v; }
   if (const char *e = getenv("POLAR_FORCE_LITERAL")) h->force_literal = atoi(e) != 0;
+  if (const char *e = getenv("POLAR_NL_DENSE")) h->nl_dense = atoi(e) != 0;

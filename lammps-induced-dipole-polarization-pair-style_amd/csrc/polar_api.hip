@@ -322,6 +322,7 @@ const void *polar_pair_extract(const polar_handle *h, const char *name, int *dim
   if (!h || !name) return nullptr;
   if (dim) *dim = 0;
   if (strcmp(name, "cut_coul") == 0) return &h->ph.st.cut_coul;
+  if (strcmp(name, "nl_dense") == 0) return &h->nl_dense_used;  // 1.0: the last list build walked dense candidate trips
   if (dim) *dim = 2;
   if (strcmp(name, "epsilon") == 0) return h->ph.epsilon.data();
   if (strcmp(name, "sigma") == 0) return h->ph.sigma.data();

@@ -245,6 +245,23 @@ __device__ __forceinline__ bool min_image_rint_w(const Box &b, double xi, double
   dx = ex; dy = ey; dz = ez;
   return nz != 0.0 || ny != 0.0 || nx != 0.0;
 }
+// The list build's form: `b` has inverse length 0 in the directions that are not periodic (rint(d * 0) = 0 and the FMA adds an
+// exact zero: the same bits without a select per direction), and "a lattice vector was taken off" comes back as a lane mask.
+template <bool TRI>
+__device__ __forceinline__ unsigned long long min_image_rint_m(const Box &b, double xi, double yi, double zi, double xj, double yj,
+                                                               double zj, double &dx, double &dy, double &dz) {
+  double ex = xi - xj, ey = yi - yj, ez = zi - zj;
+  const double nz = rint(ez * b.inv[2]);
+  ez = fma(-b.prd[2], nz, ez);
+  if (TRI) { ey = fma(-b.yz, nz, ey); ex = fma(-b.xz, nz, ex); }
+  const double ny = rint(ey * b.inv[1]);
+  ey = fma(-b.prd[1], ny, ey);
+  if (TRI) ex = fma(-b.xy, ny, ex);
+  const double nx = rint(ex * b.inv[0]);
+  ex = fma(-b.prd[0], nx, ex);
+  dx = ex; dy = ey; dz = ez;
+  return __builtin_amdgcn_ballot_w64(nz != 0.0) | __builtin_amdgcn_ballot_w64(ny != 0.0) | __builtin_amdgcn_ballot_w64(nx != 0.0);
+}
 // fractional ("lamda") coordinates of a point, src/domain.cpp x2lamda: orthogonal boxes divide by the box lengths,
 // tilted boxes back-substitute through the triangular cell matrix
 __host__ __device__ __forceinline__ void frac_coords(const Box &b, const double lo[3], double x, double y, double z, double fr[3]) {
@@ -273,6 +290,12 @@ __host__ __device__ __forceinline__ long long lp_slot(long long e, int qm = 1) {
   const long long p = e & 63;
   const long long lane = qm ? (((p & 15) << 2) | (p >> 4)) : p;
   return ((e >> 8) << 8) + (lane << 2) + ((e >> 6) & 3);
+}
+// the same in 32 bits, for entries inside one row (a pitch is far below 2^31)
+__host__ __device__ __forceinline__ unsigned lp_slot32(unsigned e, int qm) {
+  const unsigned p = e & 63u;
+  const unsigned lane = qm ? (((p & 15u) << 2) | (p >> 4)) : p;
+  return (e & ~255u) + (lane << 2) + ((e >> 6) & 3u);
 }
 
 #define POLAR_NL_SAMEMOL 0x40000000

@@ -251,7 +251,9 @@ struct polar_handle {
   bool sym_typed = false, dev_typed = false;
   int static_xq = 1;             // the static-field rows gather 32-byte {x, y, z, q} records instead of whole AtomRecs (POLAR_STATIC_XQ=0)
   int pol_first = 1;             // polarizable atoms first inside a cell (POLAR_POL_FIRST=0: arrival order)
+  double nl_dense_used = 1.0;    // the last k_nl_build walked dense candidate trips (polar_pair_extract "nl_dense"; 0: the lab library's per-run walk)
 #ifdef POLAR_LAB
+  int nl_dense = 1;              // POLAR_NL_DENSE=0: k_nl_build strides every stencil run on its own (the form before the dense trips)
   int force_literal = 0;         // the polarization force kernels run the term-by-term pair arithmetic of lab/force_pair_literal.hpp (POLAR_FORCE_LITERAL=1)
 #endif
   int part_k = 0, part_n = 1;    // polar_step_sweep_part: which share of the colour phases the next sweep_once runs

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "polar_common.hpp"
+#include "polar_nl_dense.hpp"
 
 namespace polar {
 
@@ -547,12 +548,36 @@ static __global__ void k_color_fill(long long ncell, int nclass, const long long
   }
 }
 
-// One wave per atom row; lanes stride the atoms of the <=27 distinct neighbor cells (contiguous s
-// ranges); ballot + popcount compacts in order.  Single pass into the pitched lists:
+// lanes below `lane` among the set bits of a ballot, added to `base` (two v_mbcnt)
+__device__ __forceinline__ int prefix_count(unsigned long long m, int base) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, base));
+}
+// the run table of a row atom in the lanes that worked it out (lane sr = stencil row sr), read with v_readlane
+struct NlRunLanes {
+  int s0v, k0v, s1v, k1v, endv;
+  unsigned m1;  // rows with a piece 1
+  __device__ __forceinline__ int s0(int sr) const { return __builtin_amdgcn_readlane(s0v, sr); }
+  __device__ __forceinline__ int k0(int sr) const { return __builtin_amdgcn_readlane(k0v, sr); }
+  __device__ __forceinline__ int s1(int sr) const { return __builtin_amdgcn_readlane(s1v, sr); }
+  __device__ __forceinline__ int k1(int sr) const { return __builtin_amdgcn_readlane(k1v, sr); }
+  __device__ __forceinline__ int end(int sr) const { return __builtin_amdgcn_readlane(endv, sr); }
+  __device__ __forceinline__ bool two(int sr) const { return (m1 >> sr) & 1u; }
+};
+// One wave per atom row; the lanes walk the atoms of the row's stencil of cells (contiguous s ranges) 64 at a time;
+// ballot + popcount compacts in order.  Single pass into the pitched lists:
 //   nl : every j with rsq <= cutallsq                      (static field, forces, rank metric)
 //   dd : alpha_i != 0, alpha_j != 0 and rsq < ddcutsq      (the dipole sweep stream)
 // cnt[] receives the TRUE counts; writes stop at the pitch and *overflow is raised.
-template <bool TRI, bool RECHECK>
+// DENSE (the product path): the runs of a row atom's stencil are laid end to end and walked in trips of 64 candidates
+// (polar_nl_dense.hpp) -- 28.1 trips per row on the 5x5x4 MOF-5 box instead of the 40.2 of striding every run on its own
+// (DENSE = false, the lab library's A/B partner POLAR_NL_DENSE=0).  Same candidates in the same order: the lists come
+// out entry for entry the same (tests/test_gpu_nl_dense_trips.py).
+// gfx950 -O3, dense: trip loop of <false, false> 66 vector instructions (20 FP64) + 64 scalar + 5 memory, 6 of the 66 in
+// the run-table walk (per-run form before: 72 / 20 + 45 + 5; tests/test_nl_isa_budget.py); <false, true> 72 / 21,
+// <true, false> 69 / 23, <true, true> 75 / 24.  VGPRs <false,false> 26, <false,true> 27, <true,false> 22, <true,true> 23
+// (before: 48 / 54 / 44 / 53 -- the row atom is wave-uniform now and lives in scalar registers; cap 64:
+// tests/test_kernel_resources.py).
+template <bool TRI, bool RECHECK, bool DENSE = true>
 static __global__ __launch_bounds__(POLAR_BLOCK) void k_nl_build(const int *__restrict__ rows, int nrows,
                                                           const double4 *__restrict__ pos4, Box box, CellGrid g,
                                                           const long long *__restrict__ cell_first, double cutallsq,
@@ -570,7 +595,7 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_nl_build(const int *__re
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * POLAR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (row >= nrows) return;
-  const int i = rows ? rows[row] : row;  // s space: the atoms of cell c are the indices [cell_first[c], cell_first[c+1])
+  const int i = __builtin_amdgcn_readfirstlane(rows ? rows[row] : row);  // s space: the atoms of cell c are the indices [cell_first[c], cell_first[c+1])
   const double4 ri = pos4[i];            // {x, y, z, (molecule, polarizable)}
   const int imol = __double2hiint(ri.w), ipol = __double2loint(ri.w);
   // colour re-validation on reneighbor steps (color_s != NULL): the colouring of the previous list stays in use unless
@@ -597,10 +622,22 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_nl_build(const int *__re
   const int c0 = cc[0], c1 = cc[1], c2 = cc[2];
   // lp sweep: the dd row of atom i is stored where the sweep will walk it (dd_slot[i] = its row in launch order), so that a
   // sweep wave can request its index stream before it knows which atom it works on; rows without a slot hold no dd pair
-  const int slot_i = dd_slot ? dd_slot[i] : i;
+  const int slot_i = __builtin_amdgcn_readfirstlane(dd_slot ? dd_slot[i] : i);
   const long long nl0 = (long long)i * nl_pitch, dd0 = (long long)(slot_i >= 0 ? slot_i : 0) * dd_pitch;
+  // the row's slots: a scalar base and a 32-bit byte offset per lane (pitches are far below 2^29 entries)
+  char *const nl_row = reinterpret_cast<char *>(nl_j + nl0), *const dd_row = reinterpret_cast<char *>(dd_j + dd0);
+  char *const r2_row = reinterpret_cast<char *>(dd_r2 ? dd_r2 + dd0 : nullptr);
+  const char *const pos_b = reinterpret_cast<const char *>(pos4);  // 32-byte entries, fewer than 2^27 of them (build_lists)
+  const int nl_cap = (int)nl_pitch, dd_cap = (int)dd_pitch;
+  const unsigned long long dd_im = (ipol && slot_i >= 0) ? ~0ull : 0ull;  // rows without a slot hold no dd pair
+  // directions that are not periodic get the inverse length 0: rint(d * 0) = 0 and the FMA adds an exact zero -- the same
+  // bits as selecting 0.0 per candidate, without the selects
+  Box pbox = box;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { pbox.inv[k] = box.periodic[k] ? box.inv[k] : 0.0; pbox.periodic[k] = 1; }
   int ncount = 0, dcount = 0;
-  bool wrap_lane = false;  // this lane saw a dd pair of the row that reaches across a periodic face (lp sweep: rows without skip the wrap)
+  unsigned long long wrap_m = 0ull;  // lanes that saw a dd pair of the row that reaches across a periodic face (lp sweep: rows without skip the wrap)
+  const int same_i = imol != 0 ? POLAR_NL_SAMEMOL : 0;
   // Cells have an edge >= cutoff/2, so the stencil reaches +-2 cells (125 cells hold 42 % fewer
   // candidates than 27 cells of edge >= cutoff).  Cells are stored x-fastest, so the 5 cells of a
   // stencil row are ONE contiguous run of atoms (two runs when the row wraps around the box): the
@@ -621,11 +658,14 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_nl_build(const int *__re
   const int nsr = zcnt * ycnt;
   int ra0 = 0, rb0 = 0, ra1 = 0, rb1 = 0;  // run 0: [ra0, rb0), run 1: [ra1, rb1) (s indices)
   if (lane < nsr) {
-    const int zz = zlo + lane / ycnt, yy = ylo + lane % ycnt;
+    // lane / ycnt and lane % ycnt for lane < 25, ycnt <= 5, and the wrap of a cell index in [-2, n + 1], by compare-and-add
+    // (a division by a variable costs some thirty instructions)
+    const int lz = (lane >= ycnt) + (lane >= 2 * ycnt) + (lane >= 3 * ycnt) + (lane >= 4 * ycnt);
+    const int zz = zlo + lz, yy = ylo + (lane - lz * ycnt);
     int b2 = zz, b1 = yy;
     bool ok = true;
-    if (b2 < 0 || b2 >= n2) { if (!box.periodic[2]) ok = false; b2 = (b2 + n2) % n2; }
-    if (b1 < 0 || b1 >= n1) { if (!box.periodic[1]) ok = false; b1 = (b1 + n1) % n1; }
+    if (b2 < 0 || b2 >= n2) { if (!box.periodic[2]) ok = false; b2 = b2 < 0 ? b2 + n2 : b2 - n2; }
+    if (b1 < 0 || b1 >= n1) { if (!box.periodic[1]) ok = false; b1 = b1 < 0 ? b1 + n1 : b1 - n1; }
     double dzmin = 0.0, dymin = 0.0;
     if (n2 >= 5) { const int d = zz - c2; dzmin = d > 0 ? (d - uu[2]) * edge[2] : (d < 0 ? (uu[2] - (d + 1)) * edge[2] : 0.0); }
     if (n1 >= 5) { const int d = yy - c1; dymin = d > 0 ? (d - uu[1]) * edge[1] : (d < 0 ? (uu[1] - (d + 1)) * edge[1] : 0.0); }
@@ -649,39 +689,65 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_nl_build(const int *__re
       }
     }
   }
-  for (int sr = 0; sr < nsr; sr++) {
+  // one trip: lane's candidate p (`valid`: the lane holds one).  Everything is computed as data -- an idle lane looks at the
+  // row atom itself, a valid address and never a pair -- so that the ballots read the compare results directly.
+  auto candidate = [&](const int p, const bool valid) {
+    const int j = valid ? p : i;
+    const double4 rj = *reinterpret_cast<const double4 *>(pos_b + ((unsigned)j << 5));  // consecutive lanes read consecutive 32-byte entries
+    double ex, ey, ez;
+    const unsigned long long shifted = min_image_rint_m<TRI>(pbox, ri.x, ri.y, ri.z, rj.x, rj.y, rj.z, ex, ey, ez);
+    const double rsq = ex * ex + ey * ey + ez * ez;
+    // lane masks straight from the compares, combined as scalars (a ballot of a combined predicate goes through a select
+    // and a second compare per list)
+    const unsigned long long m_pair = __builtin_amdgcn_ballot_w64(j != i);
+    const unsigned long long m_nl = m_pair & __builtin_amdgcn_ballot_w64(rsq <= cutallsq);
+    const unsigned long long m_dd = m_pair & dd_im & __builtin_amdgcn_ballot_w64(__double2loint(rj.w) != 0) & __builtin_amdgcn_ballot_w64(rsq < ddcutsq);
+    wrap_m |= m_dd & shifted;
+    const bool in_nl = (j != i) & (rsq <= cutallsq);  // (the lane's own bit of m_nl / m_dd: the same compares)
+    const bool in_dd = (j != i) & (dd_im != 0ull) & (__double2loint(rj.w) != 0) & (rsq < ddcutsq);
+    if (RECHECK) { if (icol >= 0 && j != i && rsq < colordistsq && __double2loint(rj.w) != 0 && color_s[j] == icol) clash = true; }
+    int jmol = __double2hiint(rj.w);
+    asm("" : "+v"(jmol));  // (keeps the compare on the 32-bit word: without it the compiler compares the whole 64-bit w, three instructions more)
+    const int same = imol == jmol ? same_i : 0;
+    const int kn = prefix_count(m_nl, ncount), kd = prefix_count(m_dd, dcount);
+    // bit 30 of an nl entry: "same non-zero molecule" -- the static field and the charge-dipole terms
+    // skip such pairs (PS.cpp:342,454), so those kernels need no molecule gather
+    if (in_nl && kn < nl_cap) *reinterpret_cast<int *>(nl_row + ((unsigned)kn << 2)) = j | same;
+    if (in_dd && kd < dd_cap) {
+      // lp sweep (dd_shift 6): byte offset of the 64-byte record, stored in the chunked order (lp_slot)
+      *reinterpret_cast<int *>(dd_row + ((dd_shift ? lp_slot32((unsigned)kd, dd_qm) : (unsigned)kd) << 2)) = j << dd_shift;
+      if (dd_r2) *reinterpret_cast<double *>(r2_row + ((unsigned)kd << 3)) = rsq;  // the sweep's per-pair stream value (same positions, same image rule)
+    }
+    ncount += __popcll(m_nl);
+    dcount += __popcll(m_dd);
+  };
+  if (DENSE) {
+    // the runs end to end: lane sr's stencil row starts at stream position off = sum of the lengths before it (scan over the
+    // first 32 lanes, nsr <= 25: DPP shifts inside the rows of 16 lanes, then lane 15's sum goes to the second row)
+    const int len = nl_run_len(ra0, rb0, ra1, rb1);
+    int inc = len;
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x111, 0xF, 0xF, true);  // row_shr:1, lanes without a source add 0
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x112, 0xF, 0xF, true);
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x114, 0xF, 0xF, true);
+    inc += __builtin_amdgcn_update_dpp(0, inc, 0x118, 0xF, 0xF, true);
+    const int row0 = __builtin_amdgcn_readlane(inc, 15);
+    inc += (lane >= 16 && lane < 32) ? row0 : 0;
+    const int total = __builtin_amdgcn_readlane(inc, 31);
+    const NlRunEntry e = nl_run_entry(ra0, rb0, ra1, rb1, inc - len);
+    // (lanes >= nsr hold empty runs: no bit in either mask)
+    const NlRunLanes tab{e.s0, e.k0, e.s1, e.k1, e.end, (unsigned)__ballot(rb1 > ra1)};
+    unsigned rem = (unsigned)__ballot(len > 0);
+    for (int t0 = 0; t0 < total; t0 += 64) {
+      const int g = t0 + lane;
+      const int k = nl_dense_shift(tab, rem, t0, g);
+      candidate(g + k, g < total);
+    }
+  } else {
+    for (int sr = 0; sr < nsr; sr++) {
 #pragma unroll
-    for (int piece = 0; piece < 2; piece++) {
-      const int a = __builtin_amdgcn_readlane(piece ? ra1 : ra0, sr), b = __builtin_amdgcn_readlane(piece ? rb1 : rb0, sr);
-      for (int base = a; base < b; base += 64) {
-        const int p = base + lane;
-        bool in_nl = false, in_dd = false;
-        const int j = p;
-        int same = 0;
-        double rsq = 0.0;
-        if (p < b && j != i) {
-          const double4 rj = pos4[j];  // consecutive lanes read consecutive 32-byte entries
-          double ex, ey, ez;
-          const bool shifted = min_image_rint_w<TRI>(box, ri.x, ri.y, ri.z, rj.x, rj.y, rj.z, ex, ey, ez);
-          rsq = ex * ex + ey * ey + ez * ez;
-          in_nl = rsq <= cutallsq;
-          in_dd = ipol && slot_i >= 0 && __double2loint(rj.w) && (rsq < ddcutsq);
-          if (RECHECK && icol >= 0 && rsq < colordistsq && __double2loint(rj.w) && color_s[j] == icol) clash = true;
-          wrap_lane |= in_dd && shifted;
-          same = (imol != 0 && imol == __double2hiint(rj.w)) ? POLAR_NL_SAMEMOL : 0;
-        }
-        const unsigned long long m_nl = __ballot(in_nl), m_dd = __ballot(in_dd);
-        const int kn = ncount + __popcll(m_nl & below), kd = dcount + __popcll(m_dd & below);
-        // bit 30 of an nl entry: "same non-zero molecule" -- the static field and the charge-dipole terms
-        // skip such pairs (PS.cpp:342,454), so those kernels need no molecule gather
-        if (in_nl && kn < nl_pitch) nl_j[nl0 + kn] = j | same;
-        if (in_dd && kd < dd_pitch) {
-          // lp sweep (dd_shift 6): byte offset of the 64-byte record, stored in the chunked order (lp_slot)
-          dd_j[dd0 + (dd_shift ? lp_slot(kd, dd_qm) : (long long)kd)] = j << dd_shift;
-          if (dd_r2) dd_r2[dd0 + kd] = rsq;  // the sweep's per-pair stream value (same positions, same image rule)
-        }
-        ncount += __popcll(m_nl);
-        dcount += __popcll(m_dd);
+      for (int piece = 0; piece < 2; piece++) {
+        const int a = __builtin_amdgcn_readlane(piece ? ra1 : ra0, sr), b = __builtin_amdgcn_readlane(piece ? rb1 : rb0, sr);
+        for (int base = a; base < b; base += 64) candidate(base + lane, base + lane < b);
       }
     }
   }
@@ -694,10 +760,9 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_nl_build(const int *__re
     }
   }
   if (RECHECK && color_s && __ballot(clash) != 0ull && lane == 0) atomicOr(color_conflict, 1);
-  const unsigned long long anywrap = __ballot(wrap_lane);  // all lanes are back together here
   if (lane == 0) {
     nl_cnt[i] = ncount; dd_cnt[i] = dcount;
-    if (dd_wrap) dd_wrap[i] = anywrap != 0ull;
+    if (dd_wrap) dd_wrap[i] = wrap_m != 0ull;
     if (ncount > nl_pitch || dcount > dd_pitch) atomicMax(overflow, ncount > dcount ? ncount : dcount);
     if (dcount) atomicAdd(dd_total + (blockIdx.x & 63) * 16, (unsigned long long)(dcount < dd_pitch ? dcount : (int)dd_pitch));
   }

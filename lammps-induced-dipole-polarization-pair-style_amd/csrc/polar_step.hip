@@ -181,16 +181,26 @@ void build_lists(polar_handle *h) {
     h->d_color_s.ensure(n + 1);
     k_color_map<<<nblk(n, 256), 256, 0, s>>>(n, h->d_perm.p, h->d_color_orig.p, h->d_color_s.p);
   }
-#define NLB(TRI, RC)                                                                                                          \
-  k_nl_build<TRI, RC><<<nblk(nr, POLAR_ROWS_PER_BLOCK), POLAR_BLOCK, 0, s>>>(                                                 \
+  // the list build addresses the 32-byte position entries with 32-bit byte offsets
+  if (((long long)n + 1) * (long long)sizeof(double4) >= (1ll << 32))
+    throw InputError("more than 2^27 atoms on one handle: the 32-bit position offsets of the list build would wrap (shard the system)");
+#define NLB3(TRI, RC, DENSE)                                                                                                  \
+  k_nl_build<TRI, RC, DENSE><<<nblk(nr, POLAR_ROWS_PER_BLOCK), POLAR_BLOCK, 0, s>>>(                                          \
       rows, nr, h->d_pos4.p, h->box, g, h->d_cell_first.p, cutallsq, ddsq, h->nl_pitch, h->dd_pitch, h->d_nl_cnt.p,            \
       h->d_dd_cnt.p, h->d_nl_j.p, h->d_dd_j.p, fuse ? r2p : nullptr, fuse ? 1 : 0, lp ? (6 | (h->lp_quad_major << 8)) : 0,    \
       lp ? n : -1, lp ? h->d_dd_wrap.p : nullptr, recheck ? h->d_color_s.p : nullptr, h->color_keep * h->color_keep,           \
       h->d_overflow.p + 8, lp ? h->d_slot.p : nullptr, h->d_overflow.p, h->d_ddtot.p)
+#ifdef POLAR_LAB
+#define NLB(TRI, RC) do { if (h->nl_dense) NLB3(TRI, RC, true); else NLB3(TRI, RC, false); } while (0)
+  h->nl_dense_used = h->nl_dense ? 1.0 : 0.0;
+#else
+#define NLB(TRI, RC) NLB3(TRI, RC, true)
+#endif
   // the box shape and "colours are being re-validated" are compile-time: the kernel is bound by its vector instructions
   if (h->box.triclinic) { if (recheck) NLB(true, true); else NLB(true, false); }
   else                  { if (recheck) NLB(false, true); else NLB(false, false); }
 #undef NLB
+#undef NLB3
   const RowList ddl{h->d_dd_cnt.p, h->dd_pitch};
   if (fuse || mode == 4) {
     // modes 1 and 2: the list build wrote r^2 (mode 1) and the padding itself; mode 4: no per-atom dd rows at all
