@@ -643,11 +643,11 @@ int polar_build_neighbors(polar_handle *h, const double *cutneighsq, const int *
     launch_scan(ncell, h->d_ljcell_cnt.p, h->d_ljcell_first.p, h->d_scan_a, s);
     k_lj_cell_fill<<<nblk(nall, 256), 256, 0, s>>>(nall, h->d_ljcell_id.p, h->d_ljcell_first.p, h->d_ljcell_fill.p, h->d_x.p,
                                                     h->d_type.p, h->d_mol.p, d_tag, h->d_ljpos.p, h->d_ljaux.p);
-    if (h->lj_pitch == 0 && getenv("POLAR_INIT_PITCH")) h->lj_pitch = ((std::max(64, atoi(getenv("POLAR_INIT_PITCH"))) + 63) / 64) * 64;  // tests: force the overflow path
+    if (h->lj_pitch == 0 && getenv("POLAR_INIT_PITCH")) h->lj_pitch = pitch_forced(atoi(getenv("POLAR_INIT_PITCH")));  // tests: force the overflow path
     if (h->lj_pitch == 0) {  // first build: 1.3x the mean sphere population, rounded to 64
       const double vol = std::max((h->bbox_hi[0] - h->bbox_lo[0]) * (h->bbox_hi[1] - h->bbox_lo[1]) * (h->bbox_hi[2] - h->bbox_lo[2]), 1e-9);
       const double mean = 4.18879 * cutmax * cutmax2 * nall / vol;
-      h->lj_pitch = (((long long)(1.3 * mean) + 64) / 64 + 1) * 64;
+      h->lj_pitch = pitch_first(mean, 1.3);
     }
     h->d_numneigh.ensure(n + 1); h->d_ilist.ensure(n + 1); h->d_first.ensure(n + 1);
     h->dev_typed = h->lj_typed && nall < (1 << 24) && h->ntypes < 64;
@@ -667,7 +667,7 @@ int polar_build_neighbors(polar_handle *h, const double *cutneighsq, const int *
       HIPCHECK(hipGetLastError());
       if (h->h_flags[0] == 0) break;
       if (attempt >= 3) throw std::runtime_error("polar_build_neighbors: row pitch overflow persists");
-      h->lj_pitch = ((long long)(1.25 * h->h_flags[0]) / 64 + 1) * 64;
+      h->lj_pitch = pitch_grown(h->h_flags[0]);
     }
     unsigned long long tot = 0;
     for (int k = 0; k < 64; k++) tot += h->h_ddtot[16 * k];

@@ -6,6 +6,7 @@
 //                    solve (PS.cpp:1113-1238), forces; the sweep launchers
 //   polar_color.hip  colour phases of the list-mode Gauss-Seidel (device colouring, re-validation)
 //   polar_dist.hip   multi-GPU driver over RCCL (polar_dist_*)
+// polar_plan.hpp (plain C++, tested on the host) holds the arithmetic that lays a step out: grid, pitches, k-vectors, nblk.
 // No CPU implementation of the hot path anywhere: without a GPU every compute call fails.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +33,7 @@
 
 #include "pair_host.hpp"
 #include "polar_kernels.hpp"
+#include "polar_plan.hpp"
 
 using namespace polar;
 
@@ -79,8 +81,6 @@ struct DBuf {
   }
 };
 
-// at least one workgroup: every kernel bounds-checks its index, and a zero-sized grid is a launch error
-inline int nblk(long long n, int per) { return n <= 0 ? 1 : (int)((n + per - 1) / per); }
 // one launch zeroing up to six small device buffers (sizes in bytes, multiples of 4)
 inline void zero_many(hipStream_t s, std::initializer_list<std::pair<void *, size_t>> bufs) {
   ZeroJobs jobs;
@@ -99,15 +99,6 @@ inline void zero_many(hipStream_t s, std::initializer_list<std::pair<void *, siz
 // (exclusive scans: launch_scan in polar_step.hip)
 inline int nblk_xcd(long long n, int per) { return ((nblk(n, per) + 7) / 8) * 8; }
 
-// widths of the simulation cell between opposite faces: the box lengths, or V / |face area| when the box is tilted
-inline void box_widths(const Box &b, double w[3]) {
-  w[0] = b.prd[0]; w[1] = b.prd[1]; w[2] = b.prd[2];
-  if (!b.triclinic) return;
-  const double vol = b.prd[0] * b.prd[1] * b.prd[2];
-  const double bxc[3] = {b.prd[1] * b.prd[2], -b.xy * b.prd[2], b.xy * b.yz - b.prd[1] * b.xz};  // b x c
-  w[0] = vol / std::sqrt(bxc[0] * bxc[0] + bxc[1] * bxc[1] + bxc[2] * bxc[2]);
-  w[1] = vol / (b.prd[0] * std::sqrt(b.prd[2] * b.prd[2] + b.yz * b.yz));                      // |a x c|
-}
 // squared minimum-image distance on the host (colouring, clustering): the rule of min_image_rint
 inline double min_image_dist2(const Box &b, const double *xi, const double *xj) {
   double d[3] = {xi[0] - xj[0], xi[1] - xj[1], xi[2] - xj[2]};

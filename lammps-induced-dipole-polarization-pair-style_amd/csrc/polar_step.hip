@@ -20,10 +20,9 @@ void build_cells(polar_handle *h) {
   const double cutall = std::max(st.cut_coul, st.dd_cutoff);
   double width[3];
   box_widths(h->box, width);
-  for (int k = 0; k < 3; k++)
-    if (h->box.periodic[k] && width[k] < 2.0 * cutall * (1.0 - 1e-12))
-      throw InputError("dd_cutoff mode needs box lengths >= 2*max(cut_coul,dd_cutoff); use exact mode (dd_cutoff 0)");
   CellGrid &g = h->grid;
+  if (!list_grid(width, h->box.periodic, cutall, g.nc))
+    throw InputError("dd_cutoff mode needs box lengths >= 2*max(cut_coul,dd_cutoff); use exact mode (dd_cutoff 0)");
   g.trim = 1;
 #ifdef POLAR_LAB
   if (const char *e = getenv("POLAR_NL_TRIM")) g.trim = atoi(e);
@@ -31,7 +30,6 @@ void build_cells(polar_handle *h) {
   if (h->box.triclinic) g.trim = 0;  // the per-atom stencil trimming measures orthogonal distances
   long long ncell = 1;
   for (int k = 0; k < 3; k++) {
-    g.nc[k] = std::max(1, (int)std::floor(width[k] / (0.5 * cutall)));  // cell height >= cutoff/2: +-2 stencil
     // tile sweep: the launches are the parity classes of the cells; an even count in a periodic dimension needs no third
     // class for the seam (cells grow by at most 1/6)
     if (h->sweep_kernel == 4 && k == 0 && h->tile_wide) g.nc[k] = std::max(1, (int)std::floor(width[k] / cutall));
@@ -110,33 +108,12 @@ void build_lists(polar_handle *h) {
   const double cutall = std::max(st.cut_coul, st.dd_cutoff);
   hipStream_t s = h->stream;
   const CellGrid &g = h->grid;
-  if (h->nl_pitch == 0 && getenv("POLAR_INIT_PITCH")) h->nl_pitch = h->dd_pitch = ((std::max(64, atoi(getenv("POLAR_INIT_PITCH"))) + 63) / 64) * 64;  // tests: force the overflow path
-  if (h->nl_pitch == 0) {  // first build: 1.5x the mean sphere population, rounded to 64
-    // density over the OCCUPIED part of the box (a shard handle holds one slab plus its halo, not the
-    // whole box): count the non-empty cells of a coarse host grid with edge ~cutoff
-    double vol = h->box.prd[0] * h->box.prd[1] * h->box.prd[2];
-    {
-      int nc[3];
-      long long tot = 1;
-      for (int k = 0; k < 3; k++) { nc[k] = std::max(1, std::min(64, (int)(h->box.prd[k] / cutall))); tot *= nc[k]; }
-      std::vector<char> occ((size_t)tot, 0);
-      for (int a = 0; a < n; a++) {
-        long long c = 0, mul = 1;
-        for (int k = 0; k < 3; k++) {
-          double fr = (h->hx[3 * (size_t)a + k] - h->grid.lo[k]) / h->box.prd[k];
-          fr -= std::floor(fr);
-          c += mul * std::min(nc[k] - 1, (int)(fr * nc[k]));
-          mul *= nc[k];
-        }
-        occ[(size_t)c] = 1;
-      }
-      long long filled = 0;
-      for (char v : occ) filled += v;
-      if (filled > 0) vol *= (double)filled / (double)tot;
-    }
+  if (h->nl_pitch == 0 && getenv("POLAR_INIT_PITCH")) h->nl_pitch = h->dd_pitch = pitch_forced(atoi(getenv("POLAR_INIT_PITCH")));  // tests: force the overflow path
+  if (h->nl_pitch == 0) {  // first build: 1.5x the mean sphere population, at the density of the OCCUPIED part of the box
+    const double vol = occupied_volume(n, h->hx.data(), g.lo, h->box.prd, cutall);
     h->dens = n / vol;
     double mean = n / vol * 4.18879020478639 * cutall * cutall * cutall;
-    h->nl_pitch = h->dd_pitch = (((long long)(1.5 * mean) + 64) / 64 + 1) * 64;
+    h->nl_pitch = h->dd_pitch = pitch_first(mean, 1.5);
   }
   if (h->sweep_kernel == 2) h->dd_pitch = ((h->dd_pitch + 255) / 256) * 256;  // whole 4-trip chunks (k_field_lp)
   // the lp / cluster index streams hold byte offsets j << 6 in 32-bit words: the record table must stay below 2^31 bytes
@@ -146,19 +123,9 @@ void build_lists(polar_handle *h) {
   h->d_nl_j.ensure((size_t)n * h->nl_pitch + 64);
   if (h->sweep_kernel < 3) h->d_dd_j.ensure((size_t)n * h->dd_pitch + 1024);  // slack: k_field_lp requests two index chunks per row up front
   else h->d_dd_j.ensure(64);
-  // What the sweep streams per pair.  Measured (tools/exp_nocache.sh): while index + r^2 of all pairs
-  // (12 B/pair) stay resident in the 256 MB Infinity Cache between sweeps the cached r^2 wins (36k atoms,
-  // 160 MB: 99 vs 107 us/sweep); beyond that the stream comes from HBM every sweep and rebuilding r^2 from
-  // the gathered positions wins (135k atoms, 595 MB: 320 vs 350 us/sweep).
-  int mode = h->cache_r2;
-  if (h->sweep_kernel == 1) mode = 0;
-  if (h->sweep_kernel == 2) mode = 3;  // lane-per-pair sweep: only the index (as a byte offset) is streamed
-  if (h->sweep_kernel >= 3) mode = 4;  // cluster sweep: the dd lists are the clusters' union lists (build_cluster_lists); tile sweep: build_tiles
-  if (mode < 0) {
-    const double est_pairs = h->dd_pairs > 0 ? (double)h->dd_pairs : 0.35 * (double)own_n(h) * (double)h->dd_pitch;
-    mode = (12.0 * est_pairs < 200.0e6) ? 1 : 2;
-  }
-  h->stream_mode = mode;
+  // what the sweep streams per pair (3: k_field_lp, the index alone; 4: the dd lists are the clusters' union lists
+  // (build_cluster_lists) or the tiles' (build_tiles))
+  const int mode = h->stream_mode = stream_mode(h->cache_r2, h->sweep_kernel, h->dd_pairs, own_n(h), h->dd_pitch);
   const bool r2c = mode == 1;
   if (mode == 1) h->d_dd_r2.ensure((size_t)n * h->dd_pitch + 64);
   else if (mode == 0) h->d_dd_s.ensure((size_t)n * h->dd_pitch + 64);
@@ -441,45 +408,18 @@ void launch_force(polar_handle *h, int eflag, int vglobal, double *vatom, double
 }
 
 // ---- `polar_ewald <accuracy>`: the reciprocal-space half of the Ewald static field and of its forces (polar_ewald.hpp) ----
-// LDS of k_ew_sfac: per staged atom, three power tables of nm + 1 entries and three weights; up to 32 atoms in 48 KB
-size_t ewald_lds_per_atom(int nm) { return 3 * (size_t)(nm + 1) * sizeof(double2) + 3 * sizeof(double); }
-int ewald_tile(int nm) { return (int)std::max<size_t>(1, std::min<size_t>(32, (48 * 1024) / ewald_lds_per_atom(nm))); }
+static_assert(sizeof(PlanD4) == sizeof(double4) && sizeof(PlanI4) == sizeof(int4), "polar_plan.hpp's vectors go to the device as bytes");
 
-// the half-space k-vectors with |k| <= k_cut, in (h, k, l) order, grouped in rows of consecutive l; rebuilt when the box,
-// g_ewald or the accuracy changed
-void ewald_kvectors(polar_handle *h) {
+// the k-vector table (polar_plan.hpp) on the device; rebuilt when the box, g_ewald or the accuracy changed
+void ewald_upload_kvectors(polar_handle *h) {
   const Box &b = h->box;
   const double g = h->P.g_ewald, acc = h->ph.st.polar_ewald;
   std::vector<double> key = {b.prd[0], b.prd[1], b.prd[2], b.xy, b.xz, b.yz, g, acc};
   if (key == h->ew_key) return;
-  const double lx = b.prd[0], ly = b.prd[1], lz = b.prd[2], xy = b.xy, xz = b.xz, yz = b.yz;
-  // H = [a b c] = [[lx, xy, xz], [0, ly, yz], [0, 0, lz]];  s = H^-1 r;  k = 2 pi H^-T n
-  const double i00 = 1.0 / lx, i01 = -xy / (lx * ly), i02 = (xy * yz - ly * xz) / (lx * ly * lz), i11 = 1.0 / ly,
-               i12 = -yz / (ly * lz), i22 = 1.0 / lz;
-  const double vol = lx * ly * lz, twopi = 2.0 * M_PI;
-  const double kcut = 2.0 * g * std::sqrt(-std::log(acc)), kcut2 = kcut * kcut;
-  // |n_a| <= k_cut |lattice vector a| / 2 pi
-  const int hm = (int)std::floor(kcut * lx / twopi), km = (int)std::floor(kcut * std::sqrt(xy * xy + ly * ly) / twopi),
-            lm = (int)std::floor(kcut * std::sqrt(xz * xz + yz * yz + lz * lz) / twopi);
-  std::vector<double4> kv;
-  std::vector<int4> hkl, rows;
-  for (int ih = 0; ih <= hm; ih++)
-    for (int ik = (ih == 0 ? 0 : -km); ik <= km; ik++) {
-      int row = -1;
-      for (int il = (ih == 0 && ik == 0 ? 1 : -lm); il <= lm; il++) {
-        const double kx = twopi * (ih * i00), ky = twopi * (ih * i01 + ik * i11), kz = twopi * (ih * i02 + ik * i12 + il * i22);
-        const double k2 = kx * kx + ky * ky + kz * kz;
-        if (k2 > kcut2 || k2 == 0.0) continue;
-        if (row < 0) { row = (int)rows.size(); rows.push_back(make_int4(ih, ik, il, (int)kv.size())); }
-        kv.push_back(make_double4(kx, ky, kz, 8.0 * M_PI / vol * std::exp(-k2 / (4.0 * g * g)) / k2));
-        hkl.push_back(make_int4(ih, ik, il, 0));
-      }
-    }
-  h->ew_nk = (int)kv.size();
-  h->ew_nrow = (int)rows.size();
-  rows.push_back(make_int4(0, 0, 0, h->ew_nk));
-  h->ew_nm = std::max(hm, std::max(km, lm));
-  h->ew_cell[0] = i00; h->ew_cell[1] = i01; h->ew_cell[2] = i02; h->ew_cell[3] = i11; h->ew_cell[4] = i12; h->ew_cell[5] = i22;
+  const EwaldPlan p = ewald_kvectors(b, g, acc);
+  const auto &kv = p.kv; const auto &hkl = p.hkl; const auto &rows = p.rows;
+  h->ew_nk = p.nk; h->ew_nrow = p.nrow; h->ew_nm = p.nm;
+  std::copy(p.cell, p.cell + 6, h->ew_cell);
   h->d_ew_kv.ensure(kv.size() + 1); h->d_ew_hkl.ensure(hkl.size() + 1); h->d_ew_rows.ensure(rows.size());
   h->d_ew_s.ensure(kv.size() + 1); h->d_ew_m.ensure(kv.size() + 1);
   if (!kv.empty()) {
@@ -499,21 +439,15 @@ void ewald_check(polar_handle *h, int vflag) {
   if (!(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2])) throw Unsupported("polar_ewald needs a box periodic in x, y and z");
   if (vflag & 4) throw Unsupported("polar_ewald offers no per-atom virial (vflag & 4): the reciprocal-space virial has no pairwise definition");
   if (!(h->P.g_ewald > 0.0)) throw InputError("polar_ewald needs g_ewald > 0 (polar_pair_init / polar_set_coul)");
-  ewald_kvectors(h);   // (host work and a synchronous upload, when the box, g_ewald or the accuracy changed)
+  ewald_upload_kvectors(h);   // (host work and a synchronous upload, when the box, g_ewald or the accuracy changed)
   if ((size_t)ewald_tile(h->ew_nm) * ewald_lds_per_atom(h->ew_nm) > 64 * 1024)
     throw Unsupported("polar_ewald: the k-vector range per box axis is too large for the structure-factor kernel (raise the accuracy value or g_ewald)");
 }
 
-// cut_coul beyond half the smallest distance between lattice planes: a second image of a partner can lie within cut_coul
 bool ewald_short_box(const polar_handle *h) {
-  const Box &b = h->box;
-  const double lx = b.prd[0], ly = b.prd[1], lz = b.prd[2], xy = b.xy, xz = b.xz, yz = b.yz;
-  const double vol = lx * ly * lz;
-  // plane spacings V / |b x c|, V / |c x a|, V / |a x b| of a = (lx,0,0), b = (xy,ly,0), c = (xz,yz,lz)
-  const double bc[3] = {ly * lz, -xy * lz, xy * yz - ly * xz}, ca[3] = {0.0, lx * lz, -lx * yz}, ab[3] = {0.0, 0.0, lx * ly};
-  auto nrm = [](const double *v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
-  const double w = std::min(vol / nrm(bc), std::min(vol / nrm(ca), vol / nrm(ab)));
-  return h->ph.st.cut_coul > 0.5 * w;
+  double width[3];
+  box_widths(h->box, width);
+  return ewald_short_box(width, h->ph.st.cut_coul);
 }
 
 EwCell ew_cell(const polar_handle *h) {
@@ -527,10 +461,8 @@ void ewald_sfac(polar_handle *h, bool mu, double2 *out) {
   if (nk == 0) return;
   const int tile = ewald_tile(nm);
   const size_t lds = (size_t)tile * ewald_lds_per_atom(nm);
-  const int kb = nblk(nk, 256);
-  int nchunk = std::max(1, std::min(nblk(std::max(n, 1), tile), nblk(4096, kb)));
-  const int chunk = std::max(1, nblk(std::max(n, 1), nchunk));
-  nchunk = nblk(std::max(n, 1), chunk);
+  const SfacChunks ck = ewald_sfac_chunks(n, nk, tile);
+  const int kb = ck.kb, nchunk = ck.nchunk, chunk = ck.chunk;
   h->d_ew_part.ensure((size_t)nchunk * nk);
   dim3 grid(kb, nchunk);
   if (mu) k_ew_sfac<true><<<grid, 256, lds, h->stream>>>(nk, h->d_ew_hkl.p, h->d_ew_kv.p, n, chunk, tile, nm, ew_cell(h), h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_ew_part.p);
@@ -615,10 +547,16 @@ bool accel_begin(polar_handle *h, bool ap) {
   k_accel_init<<<nblk(tot, 256), 256, 0, h->stream>>>(tot, pitch, h->d_lpdesc.p, h->d_rec0.p, h->d_acc_x.p, h->d_acc_state.p);
   return true;
 }
-void accel_export(polar_handle *h, double *dev_local_dots) {
-  const int tot = h->acc_rows, nb = nblk(tot, 256), ring = std::min(h->ph.st.polar_accel, POLAR_ACCEL_MAXM);
+// the two launches over the own rows that the forms of the mixing share: differences and their partial dot products
+// (launch_accel_diff); the mixed iterate into the records (launch_accel_mix)
+static void launch_accel_diff(polar_handle *h, int tot, int nb, int ring) {
   k_accel_diff<POLAR_ACCEL_MAXM><<<nb, 256, 0, h->stream>>>(tot, h->acc_pitch, h->d_lpdesc.p, h->d_rec0.p, h->d_scal.p, h->d_acc_state.p, h->d_acc_x.p,
                                                            h->d_acc_f.p, h->d_acc_g.p, h->d_acc_dF.p, h->d_acc_dG.p, h->d_acc_part.p, ring);
+}
+static void launch_accel_mix(polar_handle *h, int tot, int nb);   // (defined after its callers: the kernels keep their order in the code object)
+void accel_export(polar_handle *h, double *dev_local_dots) {
+  const int tot = h->acc_rows, nb = nblk(tot, 256), ring = std::min(h->ph.st.polar_accel, POLAR_ACCEL_MAXM);
+  launch_accel_diff(h, tot, nb, ring);
   k_accel_solve<POLAR_ACCEL_MAXM><<<1, 256, 0, h->stream>>>(nb, h->d_acc_part.p, h->d_scal.p, h->d_acc_state.p, dev_local_dots, nullptr, ring);
 }
 // Round 5, precision mode: the single-workgroup launches around the mixing folded together (polar_accel.hpp).
@@ -627,29 +565,34 @@ void accel_export(polar_handle *h, double *dev_local_dots) {
 // coefficients in one launch, then the mix; `diff_first`: single handle, where nothing has formed the differences yet.
 void accel_export_fused(polar_handle *h, double *ared) {
   const int tot = h->acc_rows, nb = nblk(tot, 256), ring = std::min(h->ph.st.polar_accel, POLAR_ACCEL_MAXM);
-  k_accel_diff<POLAR_ACCEL_MAXM><<<nb, 256, 0, h->stream>>>(tot, h->acc_pitch, h->d_lpdesc.p, h->d_rec0.p, h->d_scal.p, h->d_acc_state.p, h->d_acc_x.p,
-                                                           h->d_acc_f.p, h->d_acc_g.p, h->d_acc_dF.p, h->d_acc_dG.p, h->d_acc_part.p, ring);
+  launch_accel_diff(h, tot, nb, ring);
   k_accel_export<POLAR_ACCEL_MAXM><<<1, POLAR_NSLOT, 0, h->stream>>>(h->d_scal.p, h->d_slots.p, ared, 1, nb, h->d_acc_part.p, h->d_acc_state.p, ring);
 }
 void accel_decide_mix(polar_handle *h, const double *ared, bool diff_first) {
   const polar_settings &st = h->ph.st;
   const int tot = h->acc_rows, nb = nblk(tot, 256), ring = std::min(st.polar_accel, POLAR_ACCEL_MAXM);
-  if (diff_first)
-    k_accel_diff<POLAR_ACCEL_MAXM><<<nb, 256, 0, h->stream>>>(tot, h->acc_pitch, h->d_lpdesc.p, h->d_rec0.p, h->d_scal.p, h->d_acc_state.p, h->d_acc_x.p,
-                                                             h->d_acc_f.p, h->d_acc_g.p, h->d_acc_dF.p, h->d_acc_dG.p, h->d_acc_part.p, ring);
+  if (diff_first) launch_accel_diff(h, tot, nb, ring);
   k_solver_accel<POLAR_ACCEL_MAXM><<<1, POLAR_NSLOT, 0, h->stream>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.iterations_max, st.polar_precision, ared, 1, nb,
                                                                      h->d_acc_part.p, h->d_acc_state.p, ring);
-  k_accel_mix<POLAR_ACCEL_MAXM><<<nb, 256, 0, h->stream>>>(tot, h->acc_pitch, h->d_lpdesc.p, h->d_rec0.p, h->d_scal.p, h->d_acc_state.p, h->d_acc_x.p,
-                                                          h->d_acc_g.p, h->d_acc_dG.p);
+  launch_accel_mix(h, tot, nb);
 }
 void accel_step(polar_handle *h, const double *global_dots) {
   const int tot = h->acc_rows, nb = nblk(tot, 256), ring = std::min(h->ph.st.polar_accel, POLAR_ACCEL_MAXM);
-  if (!global_dots)
-    k_accel_diff<POLAR_ACCEL_MAXM><<<nb, 256, 0, h->stream>>>(tot, h->acc_pitch, h->d_lpdesc.p, h->d_rec0.p, h->d_scal.p, h->d_acc_state.p, h->d_acc_x.p,
-                                                             h->d_acc_f.p, h->d_acc_g.p, h->d_acc_dF.p, h->d_acc_dG.p, h->d_acc_part.p, ring);
+  if (!global_dots) launch_accel_diff(h, tot, nb, ring);
   k_accel_solve<POLAR_ACCEL_MAXM><<<1, 256, 0, h->stream>>>(nb, h->d_acc_part.p, h->d_scal.p, h->d_acc_state.p, nullptr, global_dots, ring);
+  launch_accel_mix(h, tot, nb);
+}
+static void launch_accel_mix(polar_handle *h, int tot, int nb) {
   k_accel_mix<POLAR_ACCEL_MAXM><<<nb, 256, 0, h->stream>>>(tot, h->acc_pitch, h->d_lpdesc.p, h->d_rec0.p, h->d_scal.p, h->d_acc_state.p, h->d_acc_x.p,
                                                           h->d_acc_g.p, h->d_acc_dG.p);
+}
+
+// end of a sweep in solve(): where the host is due a look at the device-resident loop state (look_at_state; never in a
+// fixed-iteration run) it reads it; true = the stop rule has fired
+static bool sweep_stops(polar_handle *h, int sw, int check_every) {
+  if (h->ph.st.fixed_iteration || !look_at_state(h, sw, check_every)) return false;
+  read_scal(h);
+  return h->h_scal->done != 0;
 }
 
 void solve(polar_handle *h, bool ap, polar_result *out) {
@@ -685,10 +628,7 @@ void solve(polar_handle *h, bool ap, polar_result *out) {
       const int count = (lazy && sw == max_sweeps - 2) ? max_sweeps - 1 : 1;
       if (accel && !lazy) accel_decide_mix(h, nullptr, true);   // differences, [decision + coefficients], mix: the mix is a no-op once the stop rule has fired (the result is G(x_k) of the last sweep)
       else k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision, gs ? 0 : 1, nullptr, count, det_part(h), det_npart(h));
-      if (!st.fixed_iteration && look_at_state(h, sw, check_every)) {
-        read_scal(h);
-        if (h->h_scal->done) break;
-      }
+      if (sweep_stops(h, sw, check_every)) break;
     }
   } else if (h->dense_gs) {  // exact-order blocked Gauss-Seidel on the HBM-resident tensor
     const long long np = ((long long)n + 63) / 64 * 64;   // row pitch of the component-major tensor
@@ -698,7 +638,7 @@ void solve(polar_handle *h, bool ap, polar_result *out) {
     k_dense_field<<<nblk(n, POLAR_ROWS_PER_BLOCK), POLAR_BLOCK, 0, s>>>(n, np, h->d_T6.p, h->d_rec0.p, h->d_F.p);
     // ONE launch per block of B atoms, nothing sequential inside it: d = G cb - N d' (polar_exact.hpp, k_gs_blk).  G and N
     // are formed here, once per step.
-    const int B = n >= 1024 ? 256 : n >= 384 ? 128 : 64, R = 3 * B, nb = (n + B - 1) / B;   // (at least two blocks: dense_gs needs n > 64)
+    const int B = dense_gs_block(n), R = 3 * B, nb = (n + B - 1) / B;
     const size_t RR = (size_t)R * R;
     h->d_Minv.ensure(nb * RR); h->d_gsN.ensure(nb * RR); h->d_gsAT.ensure(nb * RR); h->d_cb.ensure(3 * (size_t)n + 3);
     h->d_dmu.ensure(2 * (size_t)R + 8);
@@ -739,10 +679,7 @@ void solve(polar_handle *h, bool ap, polar_result *out) {
       }
       debug_trace(h, sw, false);
       if (!tail_on) k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision, 0, nullptr, 1, h->d_gs_part.p, npart);
-      if (!st.fixed_iteration && look_at_state(h, sw, check_every)) {
-        read_scal(h);
-        if (h->h_scal->done) break;
-      }
+      if (sweep_stops(h, sw, check_every)) break;
     }
   } else {  // exact-order blocked Gauss-Seidel, matrix-free (systems whose tensor does not fit)
     std::vector<int> order(n), pos(n);
@@ -771,10 +708,7 @@ void solve(polar_handle *h, bool ap, polar_result *out) {
       }
       debug_trace(h, sw, false);
       k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision, 0, nullptr, 1, nullptr, 0);
-      if (!st.fixed_iteration && look_at_state(h, sw, check_every)) {
-        read_scal(h);
-        if (h->h_scal->done) break;
-      }
+      if (sweep_stops(h, sw, check_every)) break;
     }
   }
 }
@@ -921,7 +855,7 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
   h->dense_gs = false;
   const bool gs_mode = (st.polar_gs || st.polar_gs_ranked) && !st.zodid;
   bool ranked_done = false;
-  if (ap && gs_mode && n > 64 && 48.0 * (double)n * (double)n <= 3.2e10 && !getenv("POLAR_NO_DENSE_GS")) {   // (n <= 64: one block, the matrix-free form; 32 GB of tensor = 25,819 atoms)
+  if (ap && gs_mode && dense_gs_fits(n) && !getenv("POLAR_NO_DENSE_GS")) {
     // exact-order Gauss-Seidel on the HBM-resident tensor: put the atoms in SWEEP order first
     // (s space = ranked order), so blocks of the sweep are contiguous rows/columns of T6
     h->dense_gs = true;
@@ -1090,8 +1024,7 @@ void tile_fallback(polar_handle *h) {
 bool grow_pitches(polar_handle *h) {
   bool again = false;
   if (h->h_flags[0] != 0) {
-    const long long need = ((long long)(1.25 * h->h_flags[0]) / 64 + 1) * 64;
-    h->nl_pitch = h->dd_pitch = std::max(need, h->nl_pitch + 64);
+    h->nl_pitch = h->dd_pitch = std::max(pitch_grown(h->h_flags[0]), h->nl_pitch + 64);
     again = true;
   }
   if (h->h_flags[4] != 0) { h->cl_pitch = (((long long)(1.25 * h->h_flags[4]) + 255) / 256) * 256; again = true; }
