@@ -145,6 +145,13 @@ double polar_pair_cut(const polar_handle *h, int itype, int jtype);
 double polar_pair_single(const polar_handle *h, double qi, double qj, int itype, int jtype, double rsq,
                          double factor_coul, double factor_lj, double *fforce);
 /* ::extract, PS.cpp:1101-1109: "cut_coul" (dim 0), "epsilon"/"sigma" (dim 2, [(n+1)*(n+1)] row-major). */
+/* Two names beyond the reference's are counters of the LAST compute call (dim 0, doubles): "lj_entries", the list entries of
+ * the rows the LJ/Coulomb kernel visited, and "lj_walked", how many of them it walked (fewer only where the rows of a
+ * symmetrised half list were cut short by their distance classes; for full lists and lists built by the library both are
+ * the length of the list).  Both are 0 before the first compute call.  Unlike the other names these two are NOT a plain
+ * lookup: the call waits for the handle's streams, may launch a small summing kernel and copies the result from the device,
+ * and it updates the handle's copy of the two numbers (the pointer returned stays valid until the next such call).  Not
+ * for use inside a step loop; NULL when the device reports an error (message in polar_last_error). */
 const void *polar_pair_extract(const polar_handle *h, const char *name, int *dim);
 int polar_get_settings(const polar_handle *h, polar_settings *out);
 

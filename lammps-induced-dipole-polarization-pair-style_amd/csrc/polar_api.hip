@@ -21,6 +21,12 @@ void upload_types(polar_handle *h, int ntypes, const double *const t[7]) {
   h->P.ljpack = h->d_lj.p;
   h->ntypes = ntypes;
   h->types_set = true;
+  // the largest pair cutoff: inside it lies class 0 of the symmetrised LJ/Coulomb rows (polar_skin.hpp); classes made for
+  // another table are not used again
+  double cmax2 = 0.0;
+  for (size_t k = 0; k < m; k++) cmax2 = std::max(cmax2, t[6][k]);
+  h->r_cmax = std::sqrt(cmax2);
+  h->skin_valid = false;
 }
 
 void upload_coul(polar_handle *h, double g_ewald, double qqrd2e, const double *slj, const double *scoul, int nbits,
@@ -72,6 +78,26 @@ void upload_coul(polar_handle *h, double g_ewald, double qqrd2e, const double *s
 
 // =============================================================================================
 namespace {
+// polar_pair_extract "lj_walked" / "lj_entries": read back when asked for, nothing per step (the one query that is not a
+// plain lookup: it waits for the streams and writes the handle's two numbers -- said so in include/polar_mi355x.h)
+void lj_counters(polar_handle *h) {
+  h->lj_walked = h->lj_entries = 0.0;
+  if (!h->have_device || !h->neigh_set || h->inum <= 0 || !h->lj_ran) return;   // (no LJ/Coulomb launch yet on the list in force: nothing was walked)
+  if (!h->lj_sym_last) { h->lj_walked = h->lj_entries = (double)h->nneigh; return; }
+  HIPCHECK(hipSetDevice(h->device));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  if (h->lj_stream) HIPCHECK(hipStreamSynchronize(h->lj_stream));
+  long long total = 0;
+  HIPCHECK(hipMemcpy(&total, h->d_sym_first.p + h->lj_rows_last, sizeof(long long), hipMemcpyDeviceToHost));
+  unsigned long long walked = (unsigned long long)total;
+  if (h->lj_walk_last) {   // the row lengths of the last step are still on the device: summed here
+    HIPCHECK(hipMemsetAsync(h->d_lj_drift.p + 1, 0, sizeof(unsigned long long), h->stream));
+    k_lj_walk_sum<<<nblk(h->lj_rows_last, 1024), 256, 0, h->stream>>>(h->lj_rows_last, h->d_lj_walk.p, h->d_lj_drift.p + 1);
+    HIPCHECK(hipMemcpyAsync(&walked, h->d_lj_drift.p + 1, sizeof(walked), hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+  }
+  h->lj_entries = (double)total; h->lj_walked = (double)walked;
+}
 // The half list of a reneighbor step on its way to the device (PS.cpp:232-247 reads list->firstneigh): rows are packed in
 // ilist order into two pinned 32 MB buffers by the helper threads -- each thread checking its entries on the way -- and a
 // buffer travels (hipMemcpyAsync from pinned memory: the full PCIe rate) while the next one is packed.  270 MB at 135k atoms:
@@ -157,7 +183,7 @@ void upload_neighbor_rows(polar_handle *h, int inum, const int *ilist, const int
   HIPCHECK(hipEventRecord(h->ev_list_up, s));
   h->list_up_pending = true;
   h->neigh_set = true;
-  h->sym_valid = false;
+  h->sym_valid = false; h->lj_ran = false;
   if (h->colors_valid) h->colors_recheck = true;  // reneighbor step: the colour phases are re-validated (k_nl_build)
   h->device_list = false;
   h->full_list = h->user_full_list;
@@ -211,6 +237,7 @@ int polar_create(int device, polar_handle **out) {
     HIPCHECK(hipStreamCreateWithFlags(&h->dl_stream, hipStreamNonBlocking));
     if (getenv("POLAR_NO_OVERLAP")) h->overlap_lj = false;
     if (const char *e = getenv("POLAR_LJ_PERS")) h->lj_pers = atoi(e);
+    if (const char *e = getenv("POLAR_LJ_SKIN")) h->lj_skin = atoi(e) != 0;   // 0: the LJ/Coulomb rows are walked whole (the A/B partner of the distance classes)
     if (const char *e = getenv("POLAR_LJ_PERS_THREADS")) h->lj_pers_threads = std::max(256, std::min(POLAR_LJ_PERS_THREADS, (atoi(e) / 64) * 64));
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess) h->ncu = ncu; }
     HIPCHECK(hipHostMalloc((void **)&h->h_scal, sizeof(Scal)));
@@ -247,6 +274,7 @@ int polar_destroy(polar_handle *h) {
     h->d_type.release(); h->d_mol.release(); h->d_order.release(); h->d_pos.release(); h->d_ilist.release();
     h->d_numneigh.release(); h->d_neigh.release(); h->d_rows.release(); h->d_first.release();
     h->d_sym_first.release(); h->d_sym_cnt.release(); h->d_sym_fill.release(); h->d_sym_j.release();
+    h->d_sym_cfirst.release(); h->d_sym_cend.release(); h->d_lj_walk.release(); h->d_sym_cls.release(); h->d_xq_snap.release(); h->d_lj_drift.release();
     h->d_mol_s.release(); h->d_perm.release(); h->d_inv.release(); h->d_rows_orig.release(); h->d_ownrows.release(); h->d_ef_s.release(); h->d_scan_a.release(); h->d_scan_b.release(); h->d_gs_cnt.release(); h->d_T6.release(); h->d_Minv.release(); h->d_gsN.release(); h->d_gsAT.release(); h->d_cb.release(); h->d_gs_part.release();
     h->d_rec0.release(); h->d_rec1.release(); h->d_scal.release(); h->d_slots.release();
     h->d_cell_id.release(); h->d_cell_cnt.release(); h->d_cell_fill.release();
@@ -323,6 +351,13 @@ const void *polar_pair_extract(const polar_handle *h, const char *name, int *dim
   if (dim) *dim = 0;
   if (strcmp(name, "cut_coul") == 0) return &h->ph.st.cut_coul;
   if (strcmp(name, "nl_dense") == 0) return &h->nl_dense_used;  // 1.0: the last list build walked dense candidate trips
+  // list entries the last step's LJ/Coulomb kernel walked / the entries of the rows it visited (equal unless the rows of a
+  // symmetrised list were cut short by their distance classes, polar_skin.hpp)
+  if (strcmp(name, "lj_walked") == 0 || strcmp(name, "lj_entries") == 0) {
+    polar_handle *m = const_cast<polar_handle *>(h);
+    if (guarded(m, [&]() { lj_counters(m); return POLAR_OK; }) != POLAR_OK) return nullptr;
+    return name[3] == 'w' ? &h->lj_walked : &h->lj_entries;
+  }
   if (dim) *dim = 2;
   if (strcmp(name, "epsilon") == 0) return h->ph.epsilon.data();
   if (strcmp(name, "sigma") == 0) return h->ph.sigma.data();
@@ -510,6 +545,9 @@ int polar_set_atoms(polar_handle *h, int nlocal, int nghost, const double *x, co
         if ((alpha[k] != 0.0) != (h->halpha[k] != 0.0)) { h->colors_valid = false; break; }
     }
     h->nlocal = nlocal; h->nghost = nghost;
+    // a symmetrised LJ/Coulomb list made for the arrays replaced here keeps no distance classes: the rows are walked whole until
+    // the next list (a list uploaded but not yet symmetrised takes its classes from the new arrays)
+    if (h->sym_valid) h->skin_valid = false;
     h->d_x.ensure(3 * nall + 3); h->d_q.ensure(nall + 1); h->d_alpha.ensure(nall + 1); h->d_type.ensure(nall + 1); h->d_mol.ensure(nall + 1);
     hipStream_t s = h->stream;
     HIPCHECK(hipMemcpyAsync(h->d_x.p, sx, 3 * nall * sizeof(double), hipMemcpyHostToDevice, s));
@@ -674,7 +712,7 @@ int polar_build_neighbors(polar_handle *h, const double *cutneighsq, const int *
     h->h_flags[0] = 0;
     k_lj_rows<<<nblk(nown, 256), 256, 0, s>>>(own_lo(h), nown, h->lj_pitch, h->d_ilist.p, h->d_first.p);
     h->inum = nown; h->nneigh = (long long)tot;
-    h->neigh_set = true; h->sym_valid = false;
+    h->neigh_set = true; h->sym_valid = false; h->lj_ran = false;
     if (h->colors_valid) h->colors_recheck = true;
     h->device_list = true; h->full_list = 1;
     return POLAR_OK;

@@ -148,6 +148,21 @@ struct polar_handle {
   DBuf<long long> d_scan_a, d_scan_b;   // workgroup totals of launch_scan: main stream / the LJ-Coulomb side stream
   DBuf<int> d_sym_cnt, d_sym_fill, d_sym_j;
   bool sym_valid = false;  // symmetrised list matches the uploaded half list
+  // distance classes of the symmetrised rows (polar_skin.hpp; built with the list): scan of the (row, class) counts, running
+  // ends of the classes per row, class of every half-list entry, the positions at that moment, this step's row lengths,
+  // {bits of the largest squared displacement since, entries walked}
+  DBuf<long long> d_sym_cfirst;
+  DBuf<int> d_sym_cend, d_lj_walk;
+  DBuf<unsigned char> d_sym_cls;
+  DBuf<double4> d_xq_snap;
+  DBuf<unsigned long long> d_lj_drift;
+  double r_cmax = 0.0;      // largest pair cutoff of the LJ table (upload_types)
+  int lj_skin = 1;          // POLAR_LJ_SKIN=0: every row is walked whole
+  bool skin_valid = false;  // classes and snapshot belong to the atoms on the device (polar_set_atoms on a list already symmetrised drops them until the next list)
+  int skin_nall = 0;        // atoms the snapshot holds
+  bool lj_ran = false;      // an LJ/Coulomb kernel has run on the list in force
+  bool lj_sym_last = false, lj_walk_last = false; int lj_rows_last = 0;   // the last a3 launch: symmetrised rows, walked by class, rows
+  double lj_walked = 0.0, lj_entries = 0.0;   // polar_pair_extract "lj_walked" / "lj_entries"
   DBuf<AtomRec> d_rec0, d_rec1;
   DBuf<Scal> d_scal;
   DBuf<double> d_slots;

@@ -5,6 +5,7 @@
 
 #include "polar_common.hpp"
 #include "polar_force_pair.hpp"
+#include "polar_skin.hpp"
 #ifdef POLAR_LAB
 #include "lab/force_pair_literal.hpp"   // the term-by-term pair arithmetic, the lab library's A/B partner (POLAR_FORCE_LITERAL=1)
 #define POLAR_LIT_PARAM , int literal
@@ -180,53 +181,159 @@ struct LJCoulParams {
   const double *ctab;     // [ntable][8]      = r, dr, f, df, e, de, c, dc  (one 64-byte line per bin)
 };
 
-// per-atom pack for the half-list loop: 32-byte {x,y,z,q} + type, locals AND ghosts, orig order
-static __global__ void k_pack_lj(int nall, const double *__restrict__ x, const double *__restrict__ q, double4 *__restrict__ xq) {
+// per-atom pack for the half-list loop: 32-byte {x,y,z,q} + type, locals AND ghosts, orig order.
+// `snap` != NULL (the rows of the symmetrised list are in distance classes, polar_skin.hpp): the positions the classes were
+// made from; the largest squared displacement since then is folded into *dmax2_bits, the bits of a non-negative double
+// (cleared by the caller; an unsigned maximum orders them like the doubles).  Atoms that have not moved issue no atomic.
+static __global__ void k_pack_lj(int nall, const double *__restrict__ x, const double *__restrict__ q, double4 *__restrict__ xq,
+                                 const double4 *__restrict__ snap, unsigned long long *__restrict__ dmax2_bits) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nall) xq[i] = make_double4(x[3 * i], x[3 * i + 1], x[3 * i + 2], q[i]);
+  double d2 = 0.0;
+  if (i < nall) {
+    const double4 p = make_double4(x[3 * i], x[3 * i + 1], x[3 * i + 2], q[i]);
+    xq[i] = p;
+    if (snap) {
+      const double4 o = snap[i];
+      const double dx = p.x - o.x, dy = p.y - o.y, dz = p.z - o.z;
+      d2 = dx * dx + dy * dy + dz * dz;
+      if (!(d2 == d2)) d2 = 1e308;   // (not a number: every class is walked, skin_walk_classes)
+    }
+  }
+  if (snap) {   // (the same in every thread; no thread has left)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) d2 = fmax(d2, __shfl_xor(d2, off, 64));
+    if ((threadIdx.x & 63) == 0 && d2 > 0.0) atomicMax(dmax2_bits, (unsigned long long)__double_as_longlong(d2));
+  }
 }
 
 // Symmetrised copy of LAMMPS' half list, built on the device when the list is uploaded: every pair
 // (i,j) of the half list appears in the row of i AND in the row of j (ghost atoms get rows too), so
 // the force loop needs no atomics on j -- the three scattered FP64 atomics per pair were 85 % of
 // the kernel.  Each row then accumulates the full force on its atom; pair tallies count 1/2 per row.
+// A row holds its entries by distance class (polar_skin.hpp: class 0 = inside the largest cutoff, then shells of the skin),
+// so that a step walks only the classes the drift since this build can have brought inside a cutoff (k_lj_walk).  The
+// displacement is the direct one, x_i - x_j with j possibly a ghost: what ljcoul_row forms.  Count pass: counts per
+// (row, class) -- the own entries of a row summed in registers, one atomic per class and row -- and the class of every
+// half-list entry as a byte, which saves the fill pass the gather.  The own entries of a (row, class) come first, in list
+// order, at places that do not depend on the order of any atomic (`fill` starts at their number); the reverse entries
+// follow in the order of the atomics, as they always did.
+// K = SKIN_CLASSES, or 1 (POLAR_LJ_SKIN=0): one class, no gather, no class bytes -- the rows as they were before the classes.
+template <int K>
 static __global__ __launch_bounds__(POLAR_BLOCK) void k_sym_count(int inum, const int *__restrict__ ilist,
                                                            const int *__restrict__ numneigh,
                                                            const long long *__restrict__ first,
-                                                           const int *__restrict__ neigh, int *__restrict__ cnt) {
+                                                           const int *__restrict__ neigh, const double4 *__restrict__ xq,
+                                                           double r_cmax, int *__restrict__ ccnt,
+                                                           unsigned char *__restrict__ cls, int *__restrict__ fill) {
+  static_assert(K == 1 || K == SKIN_CLASSES, "one class or the classes of polar_skin.hpp");
   const int lane = threadIdx.x & 63;
   const int ii = blockIdx.x * POLAR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (ii >= inum) return;
   const int i = ilist[ii];
-  const int *jl = neigh + first[i];
+  const long long f0 = first[i];
+  const int *jl = neigh + f0;
   const int jn = numneigh[i];
-  for (int jj = lane; jj < jn; jj += 64) atomicAdd(&cnt[jl[jj] & 0x3FFFFFFF], 1);
-  if (lane == 0) atomicAdd(&cnt[i], jn);
+  if (K == 1) {
+    for (int jj = lane; jj < jn; jj += 64) atomicAdd(&ccnt[jl[jj] & 0x3FFFFFFF], 1);
+    if (lane == 0) { atomicAdd(&ccnt[i], jn); fill[i] = jn; }
+    return;
+  }
+  const double4 pi = xq[i];
+  int own = 0;   // lane k < K: own entries of class k
+  for (int j0 = 0; j0 < jn; j0 += 64) {   // wave-uniform trips: the ballots below
+    const int jj = j0 + lane;
+    int c = -1;
+    if (jj < jn) {
+      const int j = jl[jj] & 0x3FFFFFFF;
+      const double4 pj = xq[j];
+      const double delx = pi.x - pj.x, dely = pi.y - pj.y, delz = pi.z - pj.z;
+      c = skin_class(delx * delx + dely * dely + delz * delz, r_cmax);
+      cls[f0 + jj] = (unsigned char)c;
+      atomicAdd(&ccnt[(size_t)j * K + c], 1);
+    }
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      const int m = __popcll(__ballot(c == k));
+      if (lane == k) own += m;
+    }
+  }
+  if (lane < K) {
+    if (own) atomicAdd(&ccnt[(size_t)i * K + lane], own);
+    fill[(size_t)i * K + lane] = own;   // (only this wave writes the cursors of row i in this pass; rows without a wave stay zero)
+  }
 }
+// after the scan of the (row, class) counts: the rows' starts as the force loop reads them (sfirst, nall + 1 entries) and
+// the running ends of the classes inside each row (cend, 4 K bytes per row, class-major: cend[k * nall + i], so that a step
+// reads the one class it needs as one contiguous array)
+template <int K>
+static __global__ void k_sym_ends(int nall, const long long *__restrict__ cfirst, long long *__restrict__ sfirst,
+                                  int *__restrict__ cend) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > nall) return;
+  const long long f0 = cfirst[(size_t)i * K];
+  sfirst[i] = f0;
+  if (i == nall || K == 1) return;
+#pragma unroll
+  for (int k = 0; k < K; k++) cend[(size_t)k * nall + i] = (int)(cfirst[(size_t)i * K + k + 1] - f0);
+}
+template <int K>
 static __global__ __launch_bounds__(POLAR_BLOCK) void k_sym_fill(int inum, const int *__restrict__ ilist,
                                                           const int *__restrict__ numneigh,
                                                           const long long *__restrict__ first,
                                                           const int *__restrict__ neigh,
-                                                          const long long *__restrict__ sfirst, int *__restrict__ fill,
-                                                          int *__restrict__ sj, const int *__restrict__ type) {
+                                                          const long long *__restrict__ cfirst, int *__restrict__ fill,
+                                                          int *__restrict__ sj, const int *__restrict__ type,
+                                                          const unsigned char *__restrict__ cls) {
   const int lane = threadIdx.x & 63;
   const int ii = blockIdx.x * POLAR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (ii >= inum) return;
   const int i = ilist[ii];
-  const int *jl = neigh + first[i];
+  const long long f0 = first[i];
+  const int *jl = neigh + f0;
   const int jn = numneigh[i];
-  // own row: one slot range per wave, entries in list order
-  long long base = 0;
-  if (lane == 0) base = sfirst[i] + atomicAdd(&fill[i], jn);
-  base = __shfl(base, 0, 64);
-  for (int jj = lane; jj < jn; jj += 64) {
-    const int e = jl[jj];
-    const int j = e & 0x3FFFFFFF;
-    // `type` != NULL (fewer than 2^24 atoms, fewer than 64 types): the partner's type rides in bits 24-29 of the entry, which
-    // saves the force loop one scattered 4-byte gather per pair (the loop is bound by its vector-memory instructions)
-    sj[base + jj] = type ? (e | (type[j] << 24)) : e;                                          // j with its special bits
-    sj[sfirst[j] + atomicAdd(&fill[j], 1)] = i | (e & 0xC0000000) | (type ? type[i] << 24 : 0);  // reverse entry, same bits
+  // lane k < K: where the row's next own entry of class k goes -- from the start of the class on, no atomic; the cursor of the
+  // reverse entries (`fill`, 32-bit, beside the scanned starts) begins behind them
+  long long base = lane < K ? cfirst[(size_t)i * K + lane] : 0;
+  for (int j0 = 0; j0 < jn; j0 += 64) {   // wave-uniform trips: the ballots below
+    const int jj = j0 + lane;
+    int c = -1, e = 0;
+    if (jj < jn) { e = jl[jj]; c = K == 1 ? 0 : cls[f0 + jj]; }
+    // own row: entries of a class in list order
+    long long slot = 0;
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      const unsigned long long m = __ballot(c == k);
+      if (m == 0) continue;   // wave-uniform
+      const long long b = __shfl(base, k, 64);
+      if (c == k) slot = b + __popcll(m & ((1ull << lane) - 1ull));
+      if (lane == k) base += __popcll(m);
+    }
+    if (c >= 0) {
+      const int j = e & 0x3FFFFFFF;
+      // `type` != NULL (fewer than 2^24 atoms, fewer than 64 types): the partner's type rides in bits 24-29 of the entry, which
+      // saves the force loop one scattered 4-byte gather per pair (the loop is bound by its vector-memory instructions)
+      sj[slot] = type ? (e | (type[j] << 24)) : e;                                          // j with its special bits
+      const size_t jc = (size_t)j * K + c;
+      sj[cfirst[jc] + atomicAdd(&fill[jc], 1)] = i | (e & 0xC0000000) | (type ? type[i] << 24 : 0);  // reverse entry, same bits
+    }
   }
+}
+// every step: how far each row is walked.  The drift scalar k_pack_lj has just folded gives k*, the number of leading classes
+// a pair inside a cutoff can be in (skin_walk_classes); walk[i] = the end of class k* - 1 of row i, which the force loop takes as
+// the row's length.
+static __global__ void k_lj_walk(int nall, const int *__restrict__ cend, const unsigned long long *__restrict__ dmax2_bits,
+                                 double r_cmax, int *__restrict__ walk) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int ks = skin_walk_classes(__longlong_as_double((long long)*dmax2_bits), r_cmax);
+  if (i < nall) walk[i] = cend[(size_t)(ks - 1) * nall + i];
+}
+// the entries the last step walked over its rows (polar_pair_extract "lj_walked": run when asked for, not per step)
+static __global__ void k_lj_walk_sum(int nrows, const int *__restrict__ walk, unsigned long long *__restrict__ sum) {
+  long long w = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nrows; i += gridDim.x * blockDim.x) w += walk[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off, 64);
+  if ((threadIdx.x & 63) == 0 && w) atomicAdd(sum, (unsigned long long)w);
 }
 
 // One wave per listed atom i.  Per pair: 1 coalesced index load, two 16-byte gathers of {x,y,z,q},

@@ -763,7 +763,6 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
     LJCoulParams P = h->P;
     P.newton_pair = h->newton_pair; P.nlocal = n; P.cut_coulsq = st.cut_coul * st.cut_coul; P.full_list = h->full_list; P.ablate = 0;
     h->d_xq.ensure(nall + 1);
-    k_pack_lj<<<nblk(nall, 256), 256, 0, s>>>(nall, h->d_x.p, h->d_q.p, h->d_xq.p);
     const size_t ljlds = (size_t)(h->ntypes + 1) * (h->ntypes + 1) * 8 * sizeof(double);
     if (ljlds > 64 * 1024) throw InputError("too many atom types for the LDS-resident LJ table (max 31)");
     dim3 block(POLAR_BLOCK);
@@ -776,18 +775,48 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
     // polarization forces -- local atoms, minimum-image displacements -- go through f.x (phase_finish)
     const bool lj_pairwise_virial = h->full_list && vmode == 2;
     if ((eatom || vatom) && !symmetrise && !h->full_list) throw InputError("per-atom tallies need the row-complete pair list");
-    if (symmetrise && !h->sym_valid && h->inum > 0) {  // once per uploaded list (reneighbor steps)
+    const bool sym_build = symmetrise && !h->sym_valid && h->inum > 0;
+    // Between two builds of the symmetrised list its rows keep the distance classes and the positions they were made from
+    // (polar_skin.hpp): the pack folds the largest displacement since into one device scalar, which never reaches the host
+    const bool skin_kept = symmetrise && !sym_build && h->sym_valid && h->skin_valid && h->skin_nall == nall;
+    if (skin_kept && h->lj_skin) {
+      HIPCHECK(hipMemsetAsync(h->d_lj_drift.p, 0, sizeof(unsigned long long), s));
+      k_pack_lj<<<nblk(nall, 256), 256, 0, s>>>(nall, h->d_x.p, h->d_q.p, h->d_xq.p, h->d_xq_snap.p, h->d_lj_drift.p);
+    } else k_pack_lj<<<nblk(nall, 256), 256, 0, s>>>(nall, h->d_x.p, h->d_q.p, h->d_xq.p, nullptr, nullptr);
+    if (sym_build) {  // once per uploaded list (reneighbor steps)
       dim3 g0(nblk(h->inum, POLAR_ROWS_PER_BLOCK));
-      h->d_sym_cnt.ensure(nall + 1); h->d_sym_fill.ensure(nall + 1); h->d_sym_first.ensure(nall + 2);
+      // POLAR_LJ_SKIN=0: one class -- the rows, and the cost of this build, as they were before the distance classes
+      const int nclass = h->lj_skin ? SKIN_CLASSES : 1;
+      const size_t nk = (size_t)nall * nclass;   // (row, class) pairs
+      h->d_sym_cnt.ensure(nk + 4); h->d_sym_fill.ensure(nk + 4); h->d_sym_cfirst.ensure(nk + 2); h->d_sym_first.ensure(nall + 2);
       h->d_sym_j.ensure(2 * (size_t)h->nneigh + 64);
-      HIPCHECK(hipMemsetAsync(h->d_sym_cnt.p, 0, (nall + 1) * sizeof(int), s));
-      HIPCHECK(hipMemsetAsync(h->d_sym_fill.p, 0, (nall + 1) * sizeof(int), s));
-      k_sym_count<<<g0, block, 0, s>>>(h->inum, h->d_ilist.p, h->d_numneigh.p, h->d_first.p, h->d_neigh.p, h->d_sym_cnt.p);
-      launch_scan(nall, h->d_sym_cnt.p, h->d_sym_first.p, h->d_scan_b, s);
+      if (h->lj_skin) {
+        h->d_sym_cend.ensure(nk + 1); h->d_lj_walk.ensure(nall + 1); h->d_sym_cls.ensure((size_t)h->nneigh + 64);
+        h->d_xq_snap.ensure(nall + 1); h->d_lj_drift.ensure(2);
+      }
+      HIPCHECK(hipMemsetAsync(h->d_sym_cnt.p, 0, (nk + 4) * sizeof(int), s));
+      HIPCHECK(hipMemsetAsync(h->d_sym_fill.p, 0, (nk + 4) * sizeof(int), s));
       h->sym_typed = h->lj_typed && nall < (1 << 24) && h->ntypes < 64;
-      k_sym_fill<<<g0, block, 0, s>>>(h->inum, h->d_ilist.p, h->d_numneigh.p, h->d_first.p, h->d_neigh.p, h->d_sym_first.p,
-                                      h->d_sym_fill.p, h->d_sym_j.p, h->sym_typed ? h->d_type.p : nullptr);
-      h->sym_valid = true;
+      const int *ty = h->sym_typed ? h->d_type.p : nullptr;
+      if (h->lj_skin) {
+        k_sym_count<SKIN_CLASSES><<<g0, block, 0, s>>>(h->inum, h->d_ilist.p, h->d_numneigh.p, h->d_first.p, h->d_neigh.p, h->d_xq.p, h->r_cmax,
+                                                     h->d_sym_cnt.p, h->d_sym_cls.p, h->d_sym_fill.p);
+        launch_scan((long long)nk, h->d_sym_cnt.p, h->d_sym_cfirst.p, h->d_scan_b, s);
+        k_sym_ends<SKIN_CLASSES><<<nblk(nall + 1, 256), 256, 0, s>>>(nall, h->d_sym_cfirst.p, h->d_sym_first.p, h->d_sym_cend.p);
+        k_sym_fill<SKIN_CLASSES><<<g0, block, 0, s>>>(h->inum, h->d_ilist.p, h->d_numneigh.p, h->d_first.p, h->d_neigh.p, h->d_sym_cfirst.p,
+                                                    h->d_sym_fill.p, h->d_sym_j.p, ty, h->d_sym_cls.p);
+        // the snapshot the drift is measured from: the records the classes were made from (no displacement yet)
+        HIPCHECK(hipMemcpyAsync(h->d_xq_snap.p, h->d_xq.p, (size_t)nall * sizeof(double4), hipMemcpyDeviceToDevice, s));
+        HIPCHECK(hipMemsetAsync(h->d_lj_drift.p, 0, sizeof(unsigned long long), s));
+      } else {
+        k_sym_count<1><<<g0, block, 0, s>>>(h->inum, h->d_ilist.p, h->d_numneigh.p, h->d_first.p, h->d_neigh.p, nullptr, 0.0,
+                                          h->d_sym_cnt.p, nullptr, h->d_sym_fill.p);
+        launch_scan((long long)nk, h->d_sym_cnt.p, h->d_sym_cfirst.p, h->d_scan_b, s);
+        k_sym_ends<1><<<nblk(nall + 1, 256), 256, 0, s>>>(nall, h->d_sym_cfirst.p, h->d_sym_first.p, nullptr);
+        k_sym_fill<1><<<g0, block, 0, s>>>(h->inum, h->d_ilist.p, h->d_numneigh.p, h->d_first.p, h->d_neigh.p, h->d_sym_cfirst.p,
+                                         h->d_sym_fill.p, h->d_sym_j.p, ty, nullptr);
+      }
+      h->sym_valid = true; h->skin_valid = h->lj_skin != 0; h->skin_nall = nall;
     }
     // newton off: ghosts receive no force and tally nothing (PS.cpp:293, ev_tally's 0.5 per LOCAL atom), so only the
     // local rows of the symmetrised list are walked: a local-ghost pair then counts 0.5, a local-local pair 0.5 + 0.5
@@ -795,8 +824,14 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
     dim3 grid(nblk(nrows_lj, POLAR_ROWS_PER_BLOCK));
     if (symmetrise) P.full_list = 1;  // rows of the symmetrised list: force on the row atom only, tallies halved
     P.typed_list = symmetrise ? (h->sym_typed ? 1 : 0) : (h->device_list && h->dev_typed ? 1 : 0);
+    // a row of the symmetrised list is walked up to the end of the last class the drift can have brought inside a cutoff
+    // (k_lj_walk; the force loop takes the length as a row's numneigh); POLAR_LJ_SKIN=0, or classes that no longer belong to
+    // the atoms: the whole row
+    const bool walk = (sym_build || skin_kept) && h->lj_skin && h->skin_valid && h->inum > 0;
+    if (walk) k_lj_walk<<<nblk(nall, 256), 256, 0, s>>>(nall, h->d_sym_cend.p, h->d_lj_drift.p, h->r_cmax, h->d_lj_walk.p);
+    h->lj_sym_last = symmetrise; h->lj_walk_last = walk; h->lj_rows_last = nrows_lj; h->lj_ran = h->inum > 0;
     const int *il = symmetrise ? nullptr : h->d_ilist.p;
-    const int *nn = symmetrise ? nullptr : h->d_numneigh.p;
+    const int *nn = symmetrise ? (walk ? h->d_lj_walk.p : nullptr) : h->d_numneigh.p;
     const long long *fi = symmetrise ? h->d_sym_first.p : h->d_first.p;
     const int *nj = symmetrise ? h->d_sym_j.p : h->d_neigh.p;
     if (h->inum > 0) {
