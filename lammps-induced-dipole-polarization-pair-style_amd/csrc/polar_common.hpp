@@ -377,25 +377,29 @@ __device__ __forceinline__ double exp_neg(double x, const ExpCoef &K) {
   return ldexp(p, (int)n);
 }
 // 1/sqrt(x), x > 0 finite: v_rsq_f64 (about 2^-23 relative) and one second-order (Newton) correction: 2^-45 = 3e-14
-// relative, four instructions (the third-order form bought 2^-69 for a fifth: the sweep is bound by its instruction count)
+// relative, four instructions (the third-order form bought 2^-69 for a fifth: the sweep is bound by its instruction count).
+// Measured on the MI355X (tests/test_gpu_math_probe.py): the seed 2^-24.2, this form 3.9e-15.
 __device__ __forceinline__ double rsqrt_pos(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   const double e = fma(-(x * y), y, 1.0);
   return fma(y * e, 0.5, y);
 }
 // the third-order form: y (1 + e/2 + 3 e^2/8), e = 1 - x y^2 <= 2^-22: 2^-69 before the last rounding, i.e. correct to an
-// ulp, five instructions.  The force kernel takes this one: its energies are sums of one-signed terms (the second-order
-// form's error is one-signed too, and eng_pol is compared to 1e-12).
+// ulp (measured: 0.98 ulp at worst), five instructions.  The force kernel takes this one: its energies are sums of one-signed
+// terms (the second-order form's error is one-signed too, and eng_pol is compared to 1e-12).
 __device__ __forceinline__ double rsqrt_pos3(double x) {
   const double y = __builtin_amdgcn_rsq(x);
   const double e = fma(-(x * y), y, 1.0);
   return fma(y * e, fma(e, 0.375, 0.5), y);
 }
 // exp(x), -700 <= x <= 0 after the clamp: round-to-nearest of x*log2(e) through the 1.5*2^52 shift (the integer lands
-// in the low word), Cody-Waite remainder, Taylor polynomial of degree DEG (|r| <= ln2/2: truncation 2.2e-13 relative at
-// degree 10, the sweep's -- the damping term e^(-ar) p(ar) it feeds is at most 0.3 of the tensor scalar, three orders
-// inside the parity tolerance -- and 1.7e-16 at degree 12, the force kernel's), and the power of two added straight into
-// the exponent field (the result stays normal: n >= -1010).
+// in the low word), Cody-Waite remainder, Taylor polynomial of degree DEG, and the power of two added straight into the
+// exponent field (the result stays normal: n >= -1010).  |r| <= ln2/2, so the first dropped term is 2.2e-13 at degree 10 (the
+// sweep's) and 1.7e-16 at degree 12 (the force kernel's) -- absolute, against e^r >= 2^-1/2: 3.1e-13 and 2.4e-16 RELATIVE.
+// Measured on the MI355X over the rounding ties of the reduction (tests/test_gpu_math_probe.py): 2.99e-13 at degree 10;
+// 3.6e-16 = 2.3 ulp at degree 12, where the roundings of the Horner steps show beside the truncation.  The damping term
+// e^(-ar) p(ar) the sweep feeds with it is at most 1 of the tensor scalar's scale r^-3 (at short range; 0.3 beyond 2.4 A at
+// damp 2.1304): tensor_scalars_lp stays within 3e-13 of scale, five orders inside the parity tolerance.
 template <int DEG = 10>
 __device__ __forceinline__ double exp_neg_fast(double x, const ExpCoef &K) {
   static_assert(DEG >= 1 && DEG <= 13, "ExpCoef holds 1/k! up to k = 13");
@@ -413,11 +417,18 @@ __device__ __forceinline__ double exp_neg_fast(double x, const ExpCoef &K) {
 
 // Dipole field tensor scalars of build_dipole_field_matrix (PS.cpp:1284-1306):
 //   T_pq = delta_pq * s3 - d_p d_q * s5,  s3 = damp1 / r^3,  s5 = 3 damp2 / r^5
+// r^-2 takes one Newton step against r2 itself (two FMAs: the residual 1 - r2 y is exact), which leaves it half an ulp from
+// 1 / r2: r^-5 = rinv r^-2 r^-2 then carries the rounding of rinv once.  As rinv (rinv rinv)^2 it carried it five times and sat
+// at 8.9 x 2^-53 of 3 r^-5 on the MI355X; now s3 and s5 stay within 8 x 2^-53 (tests/test_gpu_math_probe.py).
+__device__ __forceinline__ double rinv2_newton(double r2, double rinv) {
+  const double y = rinv * rinv;
+  return fma(y, fma(-r2, y, 1.0), y);
+}
 template <int DAMP>
 __device__ __forceinline__ void tensor_scalars(double r2, double pd, double &s3, double &s5) {
   double rinv = rsqrt(r2);
   double r = r2 * rinv;
-  double rinv2 = rinv * rinv;
+  double rinv2 = rinv2_newton(r2, rinv);
   double r3 = rinv * rinv2;
   double r5 = r3 * rinv2;
   if (DAMP == 0) {  // exponential (Thole-like) damping
@@ -437,7 +448,7 @@ template <int DAMP>
 __device__ __forceinline__ void tensor_scalars_k(double r2, double pd, const ExpCoef &K, double &s3, double &s5) {
   double rinv = rsqrt(r2);
   double r = r2 * rinv;
-  double rinv2 = rinv * rinv;
+  double rinv2 = rinv2_newton(r2, rinv);
   double r3 = rinv * rinv2;
   double r5 = r3 * rinv2;
   if (DAMP == 0) {  // exponential (Thole-like) damping
@@ -458,14 +469,23 @@ __device__ __forceinline__ void tensor_scalars_k(double r2, double pd, const Exp
 // dE_a/ddel_b = q (B1 delta_ab - B2 del_a del_b):  B1 = (erfc(g r)/r + 2g/sqrt(pi) e^{-g^2 r^2}) / r^2,
 // B2 = (3 B1 + 2g/sqrt(pi) 2 g^2 e^{-g^2 r^2}) / r^2.  An excluded pair (kept = false) takes the erf part off instead:
 // B1 - 1/r^3 and B2 - 3/r^5, written with erf so that short intramolecular distances keep their digits.
+// The Gaussian 2g/sqrt(pi) e^{-g^2 r^2} of both.  A relative error eps of the exponent moves it by g^2 r^2 eps (8.5 eps at
+// g = 0.3243, r = 9; 23 eps at g = 0.4, r = 12), so the exponent g*g*rsq carries the rounding errors of its two products along
+// (two FMAs) and the exponential is corrected by the first-order term: what is left is the rounding of exp() itself.
+// (Without it tests/test_pair_ref_host.py saw 2.2e-15 of scale per pair at r = 9 where every other instance stays below 1.5e-15.)
+__device__ __forceinline__ double ewald_gauss(double rsq, double g) {
+  const double a = g * g, alo = fma(g, g, -a);
+  const double t = a * rsq, tlo = fma(a, rsq, -t) + alo * rsq;
+  return 1.1283791670955126 * g * (exp(-t) * (1.0 - tlo));
+}
 __device__ __forceinline__ double ewald_b1(double rsq, double g, bool kept) {
   const double r = sqrt(rsq), r2inv = 1.0 / rsq;
-  const double e = 1.1283791670955126 * g * exp(-g * g * rsq);   // 2g/sqrt(pi) e^{-g^2 r^2}
+  const double e = ewald_gauss(rsq, g);
   return kept ? (erfc(g * r) / r + e) * r2inv : -(erf(g * r) / r - e) * r2inv;
 }
 __device__ __forceinline__ void ewald_b12(double rsq, double g, bool kept, double &b1, double &b2) {
   const double r = sqrt(rsq), r2inv = 1.0 / rsq;
-  const double e = 1.1283791670955126 * g * exp(-g * g * rsq);
+  const double e = ewald_gauss(rsq, g);
   b1 = kept ? (erfc(g * r) / r + e) * r2inv : -(erf(g * r) / r - e) * r2inv;
   b2 = (3.0 * b1 + 2.0 * g * g * e) * r2inv;
 }
