@@ -8,24 +8,17 @@ namespace {
 // the half-list loop reads one 64-byte line per type pair / per Coulomb bin
 void upload_types(polar_handle *h, int ntypes, const double *const t[7]) {
   need_device(h);
-  const size_t m = (size_t)(ntypes + 1) * (ntypes + 1);
-  std::vector<double> pack(8 * m, 0.0);
-  // t = lj1, lj2, lj3, lj4, offset, cut_ljsq, cutsq  ->  cutsq, cut_ljsq, lj1, lj2, lj3, lj4, offset, pad
-  for (size_t k = 0; k < m; k++) {
-    pack[8 * k + 0] = t[6][k]; pack[8 * k + 1] = t[5][k]; pack[8 * k + 2] = t[0][k]; pack[8 * k + 3] = t[1][k];
-    pack[8 * k + 4] = t[2][k]; pack[8 * k + 5] = t[3][k]; pack[8 * k + 6] = t[4][k];
-  }
-  h->d_lj.ensure(8 * m);
-  HIPCHECK(hipMemcpy(h->d_lj.p, pack.data(), 8 * m * sizeof(double), hipMemcpyHostToDevice));
+  std::vector<double> pack;
+  // the largest pair cutoff: inside it lies class 0 of the symmetrised LJ/Coulomb rows (polar_skin.hpp); classes made for
+  // another table are not used again
+  const double r_cmax = pack_lj_table(ntypes, t, pack);
+  h->d_lj.ensure(pack.size());
+  HIPCHECK(hipMemcpy(h->d_lj.p, pack.data(), pack.size() * sizeof(double), hipMemcpyHostToDevice));
   h->P.ntypes = ntypes;
   h->P.ljpack = h->d_lj.p;
   h->ntypes = ntypes;
   h->types_set = true;
-  // the largest pair cutoff: inside it lies class 0 of the symmetrised LJ/Coulomb rows (polar_skin.hpp); classes made for
-  // another table are not used again
-  double cmax2 = 0.0;
-  for (size_t k = 0; k < m; k++) cmax2 = std::max(cmax2, t[6][k]);
-  h->r_cmax = std::sqrt(cmax2);
+  h->r_cmax = r_cmax;
   h->skin_valid = false;
 }
 
@@ -35,43 +28,16 @@ void upload_coul(polar_handle *h, double g_ewald, double qqrd2e, const double *s
   h->P.g_ewald = g_ewald; h->P.qqrd2e = qqrd2e;
   for (int k = 0; k < 4; k++) { h->P.special_lj[k] = slj[k]; h->P.special_coul[k] = scoul[k]; }
   h->P.ncoultablebits = nbits; h->P.ncoulmask = mask; h->P.ncoulshiftbits = shift; h->P.tabinnersq = tabinnersq;
-  const size_t nt = nbits ? ((size_t)1 << nbits) : 1;
-  std::vector<double> pack(8 * nt, 0.0);
-  // t = r, dr, f, df, c, dc, e, de  ->  r, dr, f, df, e, de, c, dc
-  static const int order[8] = {0, 1, 2, 3, 6, 7, 4, 5};
-  if (nbits)
-    for (size_t b = 0; b < nt; b++)
-      for (int k = 0; k < 8; k++) pack[8 * b + k] = t[order[k]][b];
-  h->d_tab.ensure(8 * nt);
-  HIPCHECK(hipMemcpy(h->d_tab.p, pack.data(), 8 * nt * sizeof(double), hipMemcpyHostToDevice));
+  std::vector<double> pack;
+  pack_coul_table(nbits, t, pack);
+  h->d_tab.ensure(pack.size());
+  HIPCHECK(hipMemcpy(h->d_tab.p, pack.data(), pack.size() * sizeof(double), hipMemcpyHostToDevice));
   h->P.ctab = h->d_tab.p;
-  // How k_ljcoul_pers may find a pair's bin (polar_rows.hpp, ljcoul_row TAB): checked here, bin by bin, against the tables the
-  // caller handed over (Pair::init_tables, src/pair.cpp): r = a float whose low `shift` mantissa bits are zero and whose masked
-  // bits give the bin's own index; dr = the reciprocal of one bin step of that binade, an exact power of two.  Up to two bins may
-  // carry another dr (the last bin before the cutoff gets 1 / (cut_coulsq - r); the bin where the index wraps): they travel as
-  // parameters.  Anything else -> the tables stay in memory for r and dr (TAB 1).
-  h->P.tab_lowmask = nbits ? (1 << shift) - 1 : 0;
-  h->P.i_special[0] = h->P.i_special[1] = -1;
-  h->P.dr_special[0] = h->P.dr_special[1] = 0.0;
-  h->lj_tab_arith = false;
-  if (nbits) {
-    bool ok = shift > 0 && shift < 23;
-    int nspecial = 0;
-    for (size_t b = 0; b < nt && ok; b++) {
-      const double r = t[0][b], dr = t[1][b];
-      const float rf = (float)r;
-      int bits;
-      memcpy(&bits, &rf, sizeof(int));
-      if ((double)rf != r || (bits & h->P.tab_lowmask) != 0 || (size_t)((bits & mask) >> shift) != b) { ok = false; break; }
-      const int e = (bits >> 23) & 0xFF;
-      const double want = std::ldexp(1.0, 150 - shift - e);
-      if (dr != want) {
-        if (nspecial < 2) { h->P.i_special[nspecial] = (int)b; h->P.dr_special[nspecial] = dr; nspecial++; }
-        else ok = false;
-      }
-    }
-    h->lj_tab_arith = ok;
-  }
+  // whether k_ljcoul_pers may rebuild a bin's r and dr from the bits of (float)rsq, and the bins that need help
+  const CoulTableArith a = coul_table_arith(nbits, mask, shift, t[0], t[1]);
+  h->P.tab_lowmask = a.lowmask;
+  for (int k = 0; k < 2; k++) { h->P.i_special[k] = a.i_special[k]; h->P.dr_special[k] = a.dr_special[k]; }
+  h->lj_tab_arith = a.ok;
   h->coul_set = true;
 }
 }  // namespace
@@ -111,8 +77,8 @@ void upload_neighbor_rows(polar_handle *h, int inum, const int *ilist, const int
   // it touches the list (launch_lj).  One pinned 32-MB buffer per chunk of the list (kept for the next list; a ring beyond 2 GB).
   const int n = h->nlocal, nall = h->nlocal + h->nghost;
   if (!h->up_stream) {
-    HIPCHECK(hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
-    HIPCHECK(hipEventCreateWithFlags(&h->ev_list_up, hipEventDisableTiming));
+    h->up_stream.create(hipStreamNonBlocking);
+    h->ev_list_up.create(hipEventDisableTiming);
   }
   hipStream_t s = h->up_stream;
   HIPCHECK(hipStreamSynchronize(s));            // the previous list's transfer reads the staging buffers refilled below
@@ -151,13 +117,13 @@ void upload_neighbor_rows(polar_handle *h, int inum, const int *ilist, const int
     if (ii1 == ii0) throw InputError("a neighbor row of more than 8M entries");
     const size_t buf = chunk % kRing;
     if (buf >= h->h_nl_stage.size()) {
-      int *p = nullptr; hipEvent_t e = nullptr;
-      HIPCHECK(hipHostMalloc((void **)&p, (size_t)CH * sizeof(int)));
-      HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      h->h_nl_stage.push_back(p); h->ev_nl.push_back(e);
+      PinBuf<int> p; Event e;
+      p.ensure((size_t)CH);
+      e.create(hipEventDisableTiming);
+      h->h_nl_stage.push_back(std::move(p)); h->ev_nl.push_back(std::move(e));
     }
     if (chunk >= kRing) HIPCHECK(hipEventSynchronize(h->ev_nl[buf]));   // the transfer that last used this buffer is over
-    int *dst = h->h_nl_stage[buf];
+    int *dst = h->h_nl_stage[buf].p;
     const long long t0 = at[ii0], cnt = at[ii1] - t0;
     pool.run([&](int part) {
       // thread `part` packs the rows whose first entry lies in its share of the chunk's entries
@@ -221,28 +187,29 @@ int polar_create(int device, polar_handle **out) {
   }
   return guarded(h, [&]() {
     HIPCHECK(hipSetDevice(device));
-    HIPCHECK(hipStreamCreate(&h->stream));
-    for (auto &e : h->ev) HIPCHECK(hipEventCreate(&e));
+    h->device_set = true;
+    h->stream.create();
+    for (auto &e : h->ev) e.create();
     {
       int prio_lo = 0, prio_hi = 0;  // numerically greatest = lowest priority
       HIPCHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-      HIPCHECK(hipStreamCreateWithPriority(&h->lj_stream, hipStreamNonBlocking, prio_lo));
+      h->lj_stream.create(hipStreamNonBlocking, prio_lo);
     }
-    HIPCHECK(hipEventCreate(&h->ev_fork)); HIPCHECK(hipEventCreate(&h->ev_join));
-    HIPCHECK(hipEventCreate(&h->ev_lj0)); HIPCHECK(hipEventCreate(&h->ev_lj1));
-    HIPCHECK(hipEventCreateWithFlags(&h->ev_dl0, hipEventDisableTiming)); HIPCHECK(hipEventCreateWithFlags(&h->ev_dl1, hipEventDisableTiming));
-    HIPCHECK(hipEventCreateWithFlags(&h->ev_mu_ready, hipEventDisableTiming));
-    for (auto &e : h->ev_fchunk) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto &e : h->ev_ks) HIPCHECK(hipEventCreate(&e));
-    HIPCHECK(hipStreamCreateWithFlags(&h->dl_stream, hipStreamNonBlocking));
+    h->ev_fork.create(); h->ev_join.create();
+    h->ev_lj0.create(); h->ev_lj1.create();
+    h->ev_dl0.create(hipEventDisableTiming); h->ev_dl1.create(hipEventDisableTiming);
+    h->ev_mu_ready.create(hipEventDisableTiming);
+    for (auto &e : h->ev_fchunk) e.create(hipEventDisableTiming);
+    for (auto &e : h->ev_ks) e.create();
+    h->dl_stream.create(hipStreamNonBlocking);
     if (getenv("POLAR_NO_OVERLAP")) h->overlap_lj = false;
     if (const char *e = getenv("POLAR_LJ_PERS")) h->lj_pers = atoi(e);
     if (const char *e = getenv("POLAR_LJ_SKIN")) h->lj_skin = atoi(e) != 0;   // 0: the LJ/Coulomb rows are walked whole (the A/B partner of the distance classes)
     if (const char *e = getenv("POLAR_LJ_PERS_THREADS")) h->lj_pers_threads = std::max(256, std::min(POLAR_LJ_PERS_THREADS, (atoi(e) / 64) * 64));
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess) h->ncu = ncu; }
-    HIPCHECK(hipHostMalloc((void **)&h->h_scal, sizeof(Scal)));
-    HIPCHECK(hipHostMalloc((void **)&h->h_flags, 16 * sizeof(int)));
-    HIPCHECK(hipHostMalloc((void **)&h->h_ddtot, 64 * 16 * sizeof(unsigned long long)));
+    h->h_scal.ensure(1);
+    h->h_flags.ensure(16);
+    h->h_ddtot.ensure(64 * 16);
     h->d_overflow.ensure(16); h->d_ddtot.ensure(64 * 16);
     h->d_scal.ensure(1);
     h->d_slots.ensure((size_t)POLAR_NSLOT * POLAR_SLOT_STRIDE);
@@ -253,46 +220,6 @@ int polar_create(int device, polar_handle **out) {
 
 int polar_destroy(polar_handle *h) {
   if (!h) return POLAR_OK;
-  if (h->have_device) {
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    if (h->lj_stream) { (void)hipStreamSynchronize(h->lj_stream); (void)hipStreamDestroy(h->lj_stream); }
-    for (hipEvent_t e : {h->ev_fork, h->ev_join, h->ev_lj0, h->ev_lj1, h->ev_dl0, h->ev_dl1, h->ev_mu_ready}) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->ev_ks) if (e) (void)hipEventDestroy(e);
-    if (h->dl_stream) (void)hipStreamDestroy(h->dl_stream);
-    if (h->up_stream) { (void)hipStreamSynchronize(h->up_stream); (void)hipStreamDestroy(h->up_stream); }
-    if (h->ev_list_up) (void)hipEventDestroy(h->ev_list_up);
-    for (int *p : h->h_nl_stage) (void)hipHostFree(p);
-    for (hipEvent_t e : h->ev_nl) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->ev_fchunk) if (e) (void)hipEventDestroy(e);
-    h->d_ljpos.release(); h->d_ljaux.release(); h->d_tag.release(); h->d_nspecial.release(); h->d_special.release();
-    h->d_ljcell_id.release(); h->d_ljcell_cnt.release(); h->d_ljcell_fill.release(); h->d_ljcell_first.release(); h->d_cutneighsq.release();
-    h->d_xchg.release(); h->d_xidx.release();
-    h->d_eatom.release(); h->d_vatom.release(); h->d_dd_r2.release(); h->d_fpol.release();
-    h->d_x.release(); h->d_q.release(); h->d_alpha.release(); h->d_f.release(); h->d_ef.release(); h->d_F.release();
-    h->d_mu.release(); h->d_mu0.release(); h->d_acc_x.release(); h->d_acc_f.release(); h->d_acc_g.release(); h->d_acc_dF.release(); h->d_acc_dG.release(); h->d_acc_part.release(); h->d_acc_state.release(); h->d_bflag.release(); h->d_rank.release(); h->d_dmu.release(); h->d_tab.release(); h->d_lj.release();
-    h->d_type.release(); h->d_mol.release(); h->d_order.release(); h->d_pos.release(); h->d_ilist.release();
-    h->d_numneigh.release(); h->d_neigh.release(); h->d_rows.release(); h->d_first.release();
-    h->d_sym_first.release(); h->d_sym_cnt.release(); h->d_sym_fill.release(); h->d_sym_j.release();
-    h->d_sym_cfirst.release(); h->d_sym_cend.release(); h->d_lj_walk.release(); h->d_sym_cls.release(); h->d_xq_snap.release(); h->d_lj_drift.release();
-    h->d_mol_s.release(); h->d_perm.release(); h->d_inv.release(); h->d_rows_orig.release(); h->d_ownrows.release(); h->d_ef_s.release(); h->d_scan_a.release(); h->d_scan_b.release(); h->d_gs_cnt.release(); h->d_T6.release(); h->d_Minv.release(); h->d_gsN.release(); h->d_gsAT.release(); h->d_cb.release(); h->d_gs_part.release();
-    h->d_rec0.release(); h->d_rec1.release(); h->d_scal.release(); h->d_slots.release();
-    h->d_cell_id.release(); h->d_cell_cnt.release(); h->d_cell_fill.release();
-    h->d_nl_cnt.release(); h->d_dd_cnt.release(); h->d_dd_wrap.release(); h->d_lpdesc.release(); h->d_slot.release(); h->d_color_orig.release(); h->d_color_s.release(); h->d_trace.release(); h->d_ew_kv.release(); h->d_ew_hkl.release(); h->d_ew_rows.release(); h->d_ew_s.release(); h->d_ew_m.release(); h->d_ew_part.release(); h->d_ew_erec.release(); h->d_ew_vpart.release(); h->d_ew_out.release(); h->d_cl_orig.release(); h->d_cl_cnt.release(); h->d_cl_wrap.release(); h->d_cl_tw.release(); h->d_cl_s.release(); h->d_nl_j.release(); h->d_dd_j.release();
-    h->d_cell_first.release(); h->d_nl_first.release(); h->d_dd_first.release(); h->d_dd_s.release(); h->d_xq.release(); h->d_pos4.release();
-    h->d_overflow.release(); h->d_ddtot.release();
-    h->d_cadj.release(); h->d_cdeg.release(); h->d_ccnt.release(); h->d_cflags.release(); h->d_crelabel.release(); h->d_klist.release(); h->d_dbgf.release(); h->d_ulead.release(); h->d_udd_j.release(); h->d_upos.release(); h->d_unit.release(); h->d_udesc.release(); h->d_cprio.release(); h->d_cstat.release(); h->d_coff.release(); h->d_lp_pend.release(); h->d_lp_part.release();
-    if (h->h_cflags) (void)hipHostFree(h->h_cflags);
-    if (h->h_cstat) (void)hipHostFree(h->h_cstat);
-    if (h->h_coff) (void)hipHostFree(h->h_coff);
-    h->d_srec0.release(); h->d_srec1.release(); h->d_thdr.release(); h->d_trow.release(); h->d_un_j.release(); h->d_dd16.release(); h->d_pend.release();
-    if (h->h_flags) (void)hipHostFree(h->h_flags);
-    if (h->h_ddtot) (void)hipHostFree(h->h_ddtot);
-    if (h->h_scal) (void)hipHostFree(h->h_scal);
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
-    for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
-    if (h->stream && h->own_stream) (void)hipStreamDestroy(h->stream);
-  }
   delete h;
   return POLAR_OK;
 }
@@ -301,7 +228,7 @@ const char *polar_last_error(const polar_handle *h) { return h ? h->err.c_str() 
 const char *polar_last_warning(const polar_handle *h) { return h ? h->warn.c_str() : ""; }
 
 int polar_pair_settings(polar_handle *h, int narg, const char *const *arg) {
-  return guarded(h, [&]() { h->ph.settings(narg, arg); h->colors_valid = false; h->nl_pitch = h->dd_pitch = 0; h->cl_pitch = 0; h->un_pitch = 0; h->pitch16 = 0; return POLAR_OK; });
+  return guarded(h, [&]() { h->ph.settings(narg, arg); h->reset_plan(); return POLAR_OK; });
 }
 int polar_pair_coeff(polar_handle *h, int ntypes, int narg, const char *const *arg) {
   return guarded(h, [&]() { h->ph.coeff(ntypes, narg, arg); return POLAR_OK; });
@@ -369,66 +296,20 @@ int polar_get_settings(const polar_handle *h, polar_settings *out) {
   *out = h->ph.st;
   return POLAR_OK;
 }
-namespace {
-const int kRestartMagic = 0x524C4F50;  // 'POLR' (little endian)
-const int kRestartVersion = 2;         // 2: + deterministic, rccl_halo, polar_accel (int32) and polar_sor (double) behind the version-1 payload
-const int kRestartPayloadV1 = 4 * (int)sizeof(double) + 10 * (int)sizeof(int);
-const int kRestartPayload = kRestartPayloadV1 + 4 * (int)sizeof(int) + (int)sizeof(double);
-}
 int polar_restart_pack(const polar_handle *h, void *buf, int max_bytes) {
   if (!h) return POLAR_ERR_STATE;
-  const int total = POLAR_RESTART_HEADER_BYTES + kRestartPayload;
-  if (!buf) return total;
-  if (max_bytes < total) return POLAR_ERR_INPUT;
-  const polar_settings &st = h->ph.st;
-  char *p = (char *)buf;
-  const int head[3] = {kRestartMagic, kRestartVersion, kRestartPayload};
-  memcpy(p, head, sizeof(head)); p += sizeof(head);
-  const double d[4] = {st.polar_precision, st.polar_damp, st.polar_gamma, st.dd_cutoff};
-  memcpy(p, d, sizeof(d)); p += sizeof(d);
-  const int iv[10] = {st.iterations_max, st.damping_type, st.zodid, st.fixed_iteration, st.polar_gs, st.polar_gs_ranked,
-                      st.use_previous, st.debug, st.device_neigh, st.restart_polar};
-  memcpy(p, iv, sizeof(iv)); p += sizeof(iv);
-  const int iv2[4] = {st.deterministic, st.rccl_halo, st.polar_accel, 0};
-  memcpy(p, iv2, sizeof(iv2)); p += sizeof(iv2);
-  memcpy(p, &st.polar_sor, sizeof(double));
-  return total;
+  return restart_pack(h->ph.st, buf, max_bytes);
 }
 int polar_restart_unpack(polar_handle *h, const void *buf, int nbytes) {
   return guarded(h, [&]() {
-    if (!buf || nbytes < POLAR_RESTART_HEADER_BYTES) throw InputError("not a polarization restart record");
-    const char *p = (const char *)buf;
-    int head[3];
-    memcpy(head, p, sizeof(head)); p += sizeof(head);
-    if (head[0] != kRestartMagic) throw InputError("not a polarization restart record");
-    const bool v1 = head[1] == 1 && head[2] == kRestartPayloadV1, v2 = head[1] == kRestartVersion && head[2] == kRestartPayload;
-    if (!(v1 || v2) || nbytes < POLAR_RESTART_HEADER_BYTES + head[2])
-      throw InputError("polarization restart record of an unknown version or length");
-    double d[4]; int iv[10];
-    memcpy(d, p, sizeof(d)); p += sizeof(d);
-    memcpy(iv, p, sizeof(iv)); p += sizeof(iv);
-    polar_settings s = h->ph.st;  // the cutoffs stay as the stock record set them
-    s.polar_precision = d[0]; s.polar_damp = d[1]; s.polar_gamma = d[2]; s.dd_cutoff = d[3];
-    s.iterations_max = iv[0]; s.damping_type = iv[1]; s.zodid = iv[2]; s.fixed_iteration = iv[3]; s.polar_gs = iv[4];
-    s.polar_gs_ranked = iv[5]; s.use_previous = iv[6]; s.debug = iv[7]; s.device_neigh = iv[8]; s.restart_polar = iv[9];
-    if (v2) {  // (a version-1 record leaves these at the defaults in force)
-      int iv2[4]; double sor;
-      memcpy(iv2, p, sizeof(iv2)); p += sizeof(iv2);
-      memcpy(&sor, p, sizeof(double));
-      s.deterministic = iv2[0]; s.rccl_halo = iv2[1]; s.polar_accel = iv2[2]; s.polar_sor = sor;
-      if (!(s.polar_sor > 0.0 && s.polar_sor < 2.0) || s.polar_accel < 0 || s.polar_accel > POLAR_ACCEL_MAX) throw InputError("polarization restart record holds an illegal polar_sor / polar_accel");
-    }
-    if (s.zodid && (s.polar_gs || s.polar_gs_ranked)) throw InputError("Zodid doesn't work with polar_gs or polar_gs_ranked");
-    if (s.polar_gs && s.polar_gs_ranked) throw InputError("polar_gs and polar_gs_ranked are mutually exclusive");
-    h->ph.st = s;
-    h->colors_valid = false; h->nl_pitch = h->dd_pitch = 0; h->cl_pitch = 0; h->un_pitch = 0; h->pitch16 = 0;
+    h->ph.st = restart_unpack(h->ph.st, buf, nbytes);
+    h->reset_plan();
     return POLAR_OK;
   });
 }
 int polar_set_settings(polar_handle *h, const polar_settings *s) {
   return guarded(h, [&]() {
-    if (s->zodid && (s->polar_gs || s->polar_gs_ranked)) throw InputError("Zodid doesn't work with polar_gs or polar_gs_ranked");
-    if (s->polar_gs && s->polar_gs_ranked) throw InputError("polar_gs and polar_gs_ranked are mutually exclusive");
+    check_solver_choice(*s);
     polar_settings v = *s;
     if (v.polar_sor == 0.0) v.polar_sor = 1.0;   // a zero-initialised struct means "the reference's update", not "freeze the dipoles"
     if (!(v.polar_sor > 0.0 && v.polar_sor < 2.0)) throw InputError("polar_sor must lie in (0, 2)");
@@ -516,23 +397,13 @@ int polar_set_atoms(polar_handle *h, int nlocal, int nghost, const double *x, co
     HostPool::get().run([&](int part) {
       Ext &e = ext[part];
       const size_t a0 = std::min(nall, (size_t)part * per), a1 = std::min(nall, ((size_t)part + 1) * per);
-      memcpy(sx + 3 * a0, x + 3 * a0, 3 * (a1 - a0) * sizeof(double));
+      if (!scan_positions(x, sx, a0, a1, e.lo, e.hi)) e.bad = 1;
       memcpy(sq + a0, q + a0, (a1 - a0) * sizeof(double));
       memcpy(sa + a0, alpha + a0, (a1 - a0) * sizeof(double));
       memcpy(stype + a0, type + a0, (a1 - a0) * sizeof(int));
       memcpy(smol + a0, molecule + a0, (a1 - a0) * sizeof(int));
-      double lo[12], hi[12], acc = 0.0, amin = 0.0;
-      for (int j = 0; j < 12; j++) { lo[j] = 1e300; hi[j] = -1e300; }
-      size_t a = a0;
-      for (; a + 4 <= a1; a += 4) {
-        const double *p = x + 3 * a;
-        for (int j = 0; j < 12; j++) { const double v = p[j]; lo[j] = v < lo[j] ? v : lo[j]; hi[j] = v > hi[j] ? v : hi[j]; acc += v - v; }
-      }
-      for (; a < a1; a++)
-        for (int k = 0; k < 3; k++) { const double v = x[3 * a + k]; lo[k] = v < lo[k] ? v : lo[k]; hi[k] = v > hi[k] ? v : hi[k]; acc += v - v; }
+      double amin = 0.0;
       for (size_t k = a0; k < a1; k++) amin = alpha[k] < amin ? alpha[k] : amin;
-      for (int j = 0; j < 12; j++) { e.lo[j % 3] = std::min(e.lo[j % 3], lo[j]); e.hi[j % 3] = std::max(e.hi[j % 3], hi[j]); }
-      if (!(acc == 0.0)) e.bad = 1;
       if (amin < 0.0) e.neg = 1;
     }, nparts);
     for (const auto &e : ext) {
@@ -590,20 +461,7 @@ int polar_set_positions(polar_handle *h, int nlocal, int nghost, const double *x
     HostPool::get().run([&](int part) {
       Ext &e = ext[part];
       const size_t a0 = std::min(nall, (size_t)part * per), a1 = std::min(nall, ((size_t)part + 1) * per);
-      memcpy(st + 3 * a0, x + 3 * a0, 3 * (a1 - a0) * sizeof(double));
-      // four atoms = twelve doubles at a time: twelve independent running minima / maxima (the compiler keeps them in vector
-      // registers; one accumulator per coordinate, fed with a stride of three, ran at a fifth of the copy's rate)
-      double lo[12], hi[12], acc = 0.0;
-      for (int j = 0; j < 12; j++) { lo[j] = 1e300; hi[j] = -1e300; }
-      size_t a = a0;
-      for (; a + 4 <= a1; a += 4) {
-        const double *p = x + 3 * a;
-        for (int j = 0; j < 12; j++) { const double v = p[j]; lo[j] = v < lo[j] ? v : lo[j]; hi[j] = v > hi[j] ? v : hi[j]; acc += v - v; }
-      }
-      for (; a < a1; a++)
-        for (int k = 0; k < 3; k++) { const double v = x[3 * a + k]; lo[k] = v < lo[k] ? v : lo[k]; hi[k] = v > hi[k] ? v : hi[k]; acc += v - v; }
-      for (int j = 0; j < 12; j++) { e.lo[j % 3] = std::min(e.lo[j % 3], lo[j]); e.hi[j % 3] = std::max(e.hi[j % 3], hi[j]); }
-      if (!(acc == 0.0)) e.bad = 1;   // (v - v is 0 for a finite v, NaN for an infinite or NaN one)
+      if (!scan_positions(x, st, a0, a1, e.lo, e.hi)) e.bad = 1;
     }, nparts);
     for (int k = 0; k < 3; k++) { h->bbox_lo[k] = 1e300; h->bbox_hi[k] = -1e300; }
     for (const auto &e : ext) {
@@ -655,14 +513,7 @@ int polar_build_neighbors(polar_handle *h, const double *cutneighsq, const int *
     const double cutmax = std::sqrt(cutmax2);
     // grid over the bounding box of locals + ghosts (recorded by polar_set_atoms), cell edge >= cutmax / 2
     LJGrid g;
-    long long ncell = 1;
-    for (int k = 0; k < 3; k++) {
-      const double ext = std::max(h->bbox_hi[k] - h->bbox_lo[k], 1e-9);
-      int nc = (int)std::floor(ext / (0.5 * cutmax));
-      nc = std::max(1, std::min(nc, 512));
-      g.nc[k] = nc; g.lo[k] = h->bbox_lo[k]; g.inv[k] = nc / ext;
-      ncell *= nc;
-    }
+    const long long ncell = lj_grid(h->bbox_lo, h->bbox_hi, cutmax, g);
     h->d_ljcell_id.ensure(nall + 1); h->d_ljcell_cnt.ensure(ncell + 1); h->d_ljcell_fill.ensure(ncell + 1); h->d_ljcell_first.ensure(ncell + 2);
     h->d_ljpos.ensure(nall + 1); h->d_ljaux.ensure(nall + 1); h->d_cutneighsq.ensure((size_t)w * w);
     HIPCHECK(hipMemcpyAsync(h->d_cutneighsq.p, cutneighsq, (size_t)w * w * sizeof(double), hipMemcpyHostToDevice, s));
@@ -682,11 +533,7 @@ int polar_build_neighbors(polar_handle *h, const double *cutneighsq, const int *
     k_lj_cell_fill<<<nblk(nall, 256), 256, 0, s>>>(nall, h->d_ljcell_id.p, h->d_ljcell_first.p, h->d_ljcell_fill.p, h->d_x.p,
                                                     h->d_type.p, h->d_mol.p, d_tag, h->d_ljpos.p, h->d_ljaux.p);
     if (h->lj_pitch == 0 && getenv("POLAR_INIT_PITCH")) h->lj_pitch = pitch_forced(atoi(getenv("POLAR_INIT_PITCH")));  // tests: force the overflow path
-    if (h->lj_pitch == 0) {  // first build: 1.3x the mean sphere population, rounded to 64
-      const double vol = std::max((h->bbox_hi[0] - h->bbox_lo[0]) * (h->bbox_hi[1] - h->bbox_lo[1]) * (h->bbox_hi[2] - h->bbox_lo[2]), 1e-9);
-      const double mean = 4.18879 * cutmax * cutmax2 * nall / vol;
-      h->lj_pitch = pitch_first(mean, 1.3);
-    }
+    if (h->lj_pitch == 0) h->lj_pitch = lj_first_pitch(h->bbox_lo, h->bbox_hi, cutmax2, nall);  // first build: 1.3x the mean sphere population
     h->d_numneigh.ensure(n + 1); h->d_ilist.ensure(n + 1); h->d_first.ensure(n + 1);
     h->dev_typed = h->lj_typed && nall < (1 << 24) && h->ntypes < 64;
     const size_t lds = (size_t)w * w * sizeof(double);
@@ -699,17 +546,17 @@ int polar_build_neighbors(polar_handle *h, const double *cutneighsq, const int *
           own_lo(h), nown, h->ntypes, h->d_x.p, h->d_type.p, h->d_mol.p, h->d_ljpos.p, h->d_ljaux.p, g, h->d_ljcell_first.p,
           h->d_cutneighsq.p, h->box, exclude_molecule_intra, d_nsp, d_sp, maxspecial, special_flag[1], special_flag[2],
           special_flag[3], h->lj_pitch, h->d_numneigh.p, h->d_neigh.p, h->d_overflow.p, h->d_ddtot.p, h->dev_typed ? 1 : 0);
-      HIPCHECK(hipMemcpyAsync(h->h_flags, h->d_overflow.p, sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHECK(hipMemcpyAsync(h->h_ddtot, h->d_ddtot.p, 64 * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipMemcpyAsync(h->h_flags.p, h->d_overflow.p, sizeof(int), hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipMemcpyAsync(h->h_ddtot.p, h->d_ddtot.p, 64 * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
       HIPCHECK(hipStreamSynchronize(s));
       HIPCHECK(hipGetLastError());
-      if (h->h_flags[0] == 0) break;
+      if (h->h_flags.p[0] == 0) break;
       if (attempt >= 3) throw std::runtime_error("polar_build_neighbors: row pitch overflow persists");
-      h->lj_pitch = pitch_grown(h->h_flags[0]);
+      h->lj_pitch = pitch_grown(h->h_flags.p[0]);
     }
     unsigned long long tot = 0;
-    for (int k = 0; k < 64; k++) tot += h->h_ddtot[16 * k];
-    h->h_flags[0] = 0;
+    for (int k = 0; k < 64; k++) tot += h->h_ddtot.p[16 * k];
+    h->h_flags.p[0] = 0;
     k_lj_rows<<<nblk(nown, 256), 256, 0, s>>>(own_lo(h), nown, h->lj_pitch, h->d_ilist.p, h->d_first.p);
     h->inum = nown; h->nneigh = (long long)tot;
     h->neigh_set = true; h->sym_valid = false; h->lj_ran = false;
@@ -845,9 +692,8 @@ int polar_upload_mu(polar_handle *h, const double *mu, long long n) {
 int polar_set_stream(polar_handle *h, void *hip_stream) {
   return guarded(h, [&]() {
     need_device(h);
-    if (h->own_stream && h->stream) { HIPCHECK(hipStreamSynchronize(h->stream)); HIPCHECK(hipStreamDestroy(h->stream)); }
-    h->stream = (hipStream_t)hip_stream;
-    h->own_stream = false;
+    if (h->stream.own_stream && h->stream) HIPCHECK(hipStreamSynchronize(h->stream));
+    h->stream.borrow((hipStream_t)hip_stream);   // (lets go of the stream it replaces, if that one was the library's)
     return POLAR_OK;
   });
 }
@@ -951,13 +797,14 @@ int polar_set_positions_range(polar_handle *h, int lo, int hi, const double *x) 
     if (!h->atoms_set || lo < 0 || hi < lo || hi > h->nlocal + h->nghost) throw InputError("polar_set_positions_range: range outside the atoms of the last polar_set_atoms");
     if (hi > lo && !x) throw InputError("polar_set_positions_range: null pointer");
     const size_t cnt = 3 * (size_t)(hi - lo);
-    for (size_t k = 0; k < cnt; k++) if (!(x[k] - x[k] == 0.0)) throw InputError("non-finite atom coordinate");
     double *st = staging(h, 3 * ((size_t)h->nlocal + h->nghost) + 6 * (size_t)h->nlocal);
     if (cnt) {
-      memcpy(st, x, cnt * sizeof(double));
+      // the box the handle has keeps growing (the other atoms are where they were); a refused range leaves it as it was
+      double blo[3] = {h->bbox_lo[0], h->bbox_lo[1], h->bbox_lo[2]}, bhi[3] = {h->bbox_hi[0], h->bbox_hi[1], h->bbox_hi[2]};
+      if (!scan_positions(x, st, 0, (size_t)(hi - lo), blo, bhi)) throw InputError("non-finite atom coordinate");
+      for (int k = 0; k < 3; k++) { h->bbox_lo[k] = blo[k]; h->bbox_hi[k] = bhi[k]; }
       HIPCHECK(hipMemcpyAsync(h->d_x.p + 3 * (size_t)lo, st, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
       for (int a = lo; a < std::min(hi, h->nlocal); a++) for (int k = 0; k < 3; k++) h->hx[3 * (size_t)a + k] = x[3 * (size_t)(a - lo) + k];
-      for (int a = lo; a < hi; a++) for (int k = 0; k < 3; k++) { const double v = x[3 * (size_t)(a - lo) + k]; h->bbox_lo[k] = std::min(h->bbox_lo[k], v); h->bbox_hi[k] = std::max(h->bbox_hi[k], v); }
       HIPCHECK(hipStreamSynchronize(h->stream));   // (the staging area is the caller's to reuse)
     }
     return POLAR_OK;
@@ -1003,9 +850,9 @@ int polar_step_state(polar_handle *h, int *done, int *iterations, int *status) {
   return guarded(h, [&]() {
     need_device(h);
     read_scal(h);
-    if (done) *done = h->h_scal->done;
-    if (iterations) *iterations = h->h_scal->iterations;
-    if (status) *status = h->h_scal->status;
+    if (done) *done = h->h_scal.p->done;
+    if (iterations) *iterations = h->h_scal.p->iterations;
+    if (status) *status = h->h_scal.p->status;
     return POLAR_OK;
   });
 }

@@ -37,10 +37,10 @@ int color_stats(polar_handle *h, bool ranked) {
   hipStream_t s = h->stream;
   HIPCHECK(hipMemsetAsync(h->d_cstat.p, 0, 128 * sizeof(double), s));
   k_color_stats<<<nblk(n, 256), 256, 0, s>>>(n, h->d_color_s.p, ranked ? h->d_rank.p : nullptr, h->d_cstat.p, h->d_perm.p, own_lo(h), own_lo(h) + own_n(h));
-  HIPCHECK(hipMemcpyAsync(h->h_cstat, h->d_cstat.p, 128 * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(h->h_cstat.p, h->d_cstat.p, 128 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
   int nc = 0;
-  for (int c = 0; c < 64; c++) if (h->h_cstat[2 * c] > 0.0) nc = c + 1;
+  for (int c = 0; c < 64; c++) if (h->h_cstat.p[2 * c] > 0.0) nc = c + 1;
   return nc;
 }
 // stage 1: buffers and the conflict lists.  color_s = -1 everywhere afterwards.
@@ -49,11 +49,7 @@ void color_adjacency(polar_handle *h, bool with_halo) {
   hipStream_t s = h->stream;
   Lap lap(s);
   lap("(work queued before)");
-  if (!h->h_cflags) {
-    HIPCHECK(hipHostMalloc((void **)&h->h_cflags, 96 * sizeof(int)));
-    HIPCHECK(hipHostMalloc((void **)&h->h_cstat, 128 * sizeof(double)));
-    HIPCHECK(hipHostMalloc((void **)&h->h_coff, POLAR_MAX_CLASS_OFF * sizeof(long long)));
-  }
+  h->h_cflags.ensure(96); h->h_cstat.ensure(128); h->h_coff.ensure(POLAR_MAX_CLASS_OFF);
   h->d_cdeg.ensure(n + 1); h->d_cprio.ensure(n + 1);
   h->d_color_s.ensure(n + 1); h->d_color_orig.ensure(n + 1); h->d_cflags.ensure(96); h->d_cstat.ensure(128); h->d_crelabel.ensure(64);
   int *flags = h->d_cflags.p;  // [0] conflict-list overflow, [1] atoms deferred in the last round, [2] a row that saw 64 colours, [65..] atoms that could not leave a folded class
@@ -74,11 +70,11 @@ void color_adjacency(polar_handle *h, bool with_halo) {
     HIPCHECK(hipMemsetAsync(flags, 0, 96 * sizeof(int), s));
     k_color_adj<<<nblk(n, 128), 128, 0, s>>>(n, h->d_pos4.p, h->d_perm.p, lo, hi, h->box, h->grid, h->d_cell_first.p, h->d_cell_fill.p, dc2,
                                              h->cadj_pitch, h->d_cadj.p, h->d_cdeg.p, h->d_cprio.p, h->d_color_s.p, flags, with_halo ? 1 : 0, sw);
-    HIPCHECK(hipMemcpyAsync(h->h_cflags, flags, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(h->h_cflags.p, flags, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
-    if (h->h_cflags[0] <= h->cadj_pitch) break;
-    if (h->h_cflags[0] > 62 || attempt > 3) throw std::runtime_error("colouring: more than 62 polarizable atoms within the colour distance of one atom (64 colours at most): reduce POLAR_COLOR_DIST");
-    h->cadj_pitch = (h->h_cflags[0] + 4 + 7) / 8 * 8;
+    if (h->h_cflags.p[0] <= h->cadj_pitch) break;
+    if (h->h_cflags.p[0] > 62 || attempt > 3) throw std::runtime_error("colouring: more than 62 polarizable atoms within the colour distance of one atom (64 colours at most): reduce POLAR_COLOR_DIST");
+    h->cadj_pitch = (h->h_cflags.p[0] + 4 + 7) / 8 * 8;
   }
   lap("conflict lists");
 }
@@ -130,10 +126,10 @@ int color_assign(polar_handle *h, bool ranked) {
       k_color_round<<<nblk(n, 256), 256, 0, s>>>(n, ap_, h->d_cadj.p, h->d_cdeg.p, h->d_cprio.p, h->d_color_s.p, flags + 1);
     }
     rounds += batch;
-    HIPCHECK(hipMemcpyAsync(h->h_cflags, flags, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(h->h_cflags.p, flags, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
-    if (h->h_cflags[2] >= 1000) throw std::runtime_error("colouring needs more than 64 colours: reduce POLAR_COLOR_DIST");
-    coloured = h->h_cflags[1] == 0;
+    if (h->h_cflags.p[2] >= 1000) throw std::runtime_error("colouring needs more than 64 colours: reduce POLAR_COLOR_DIST");
+    coloured = h->h_cflags.p[1] == 0;
   }
   if (!coloured) throw std::runtime_error("colouring: Jones-Plassmann did not finish");
   lap("cell pass + rounds");
@@ -156,13 +152,13 @@ int color_assign(polar_handle *h, bool ranked) {
   // (only a SMALL top class of at most six is worth it -- at most 2 % of the rows: where atoms overlap, e.g. sorbates flying through the
   //  framework in bench.py's ballistic leg, the extra classes are needed and no local search removes them)
   const double krows = std::min((double)kcap, 0.02 * (double)own_n(h));
-  for (int hops = 1; hops <= 3 && ncolors > 2 && ncolors <= 6 && h->h_cstat[2 * (ncolors - 1)] <= (hops < 3 ? krows : 128.0); hops++) {   // (the last, long search only for a handful of rows)
+  for (int hops = 1; hops <= 3 && ncolors > 2 && ncolors <= 6 && h->h_cstat.p[2 * (ncolors - 1)] <= (hops < 3 ? krows : 128.0); hops++) {   // (the last, long search only for a handful of rows)
     h->d_klist.ensure(4 * (size_t)kcap + 8);
     int *raw = h->d_klist.p, *list = raw + kcap, *st0 = raw + 2 * kcap, *st1 = raw + 3 * kcap, *cnt = raw + 4 * kcap;
     HIPCHECK(hipMemsetAsync(cnt, 0, sizeof(int), s));
     k_color_collect<<<nblk(n, 256), 256, 0, s>>>(n, ncolors - 1, h->d_color_s.p, kcap, raw, cnt);
     k_sort_small<<<8, 256, 0, s>>>(cnt, kcap, raw, list, st0, st1);
-    const int waves = (int)h->h_cstat[2 * (ncolors - 1)];
+    const int waves = (int)h->h_cstat.p[2 * (ncolors - 1)];
     const double reach = (2 * hops + 1) * h->color_dist;
     const int budget = hops == 1 ? 768 : hops == 2 ? 2048 : 8192;   // search steps per ball: the later stages see few rows
     for (int round = 0; round < 2 + 2 * hops; round++)
@@ -182,7 +178,7 @@ int color_assign(polar_handle *h, bool ranked) {
     std::iota(ord.begin(), ord.end(), 0);
     if (ig % 2 == 0) std::reverse(ord.begin(), ord.end());                                    // highest class first
     else std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {                         // smallest / largest class first
-      return (ig % 4 == 1) ? h->h_cstat[2 * a] < h->h_cstat[2 * b] : h->h_cstat[2 * a] > h->h_cstat[2 * b]; });
+      return (ig % 4 == 1) ? h->h_cstat.p[2 * a] < h->h_cstat.p[2 * b] : h->h_cstat.p[2 * a] > h->h_cstat.p[2 * b]; });
     for (int c = 0; c < ncolors; c++) rank[ord[c]] = c;
     HIPCHECK(hipMemcpyAsync(h->d_crelabel.p, rank.data(), 64 * sizeof(int), hipMemcpyHostToDevice, s));
     k_color_regroup<<<nblk(n, 256), 256, 0, s>>>(n, h->d_cdeg.p, h->d_crelabel.p, h->d_perm.p, h->d_color_s.p, h->d_cprio.p);
@@ -208,7 +204,7 @@ void color_finish(polar_handle *h, bool ranked, int ncolors) {
   // change first); otherwise by descending size
   std::vector<int> ord((size_t)ncolors), relabel(64, 0);
   std::iota(ord.begin(), ord.end(), 0);
-  auto key = [&](int c) { return ranked ? h->h_cstat[2 * c + 1] / std::max(h->h_cstat[2 * c], 1.0) : h->h_cstat[2 * c]; };
+  auto key = [&](int c) { return ranked ? h->h_cstat.p[2 * c + 1] / std::max(h->h_cstat.p[2 * c], 1.0) : h->h_cstat.p[2 * c]; };
   std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return key(a) > key(b); });
   for (int c = 0; c < ncolors; c++) relabel[ord[c]] = c;
   HIPCHECK(hipMemcpyAsync(h->d_crelabel.p, relabel.data(), 64 * sizeof(int), hipMemcpyHostToDevice, s));
@@ -225,13 +221,13 @@ void color_finish(polar_handle *h, bool ranked, int ncolors) {
   k_color_cellcount<<<nblk(ncell, 128), 128, 0, s>>>(ncell, nclass, h->d_cell_first.p, h->d_cell_fill.p, h->d_color_s.p, h->d_ccnt.p, h->d_perm.p, lo, hi, sub, nsub);
   launch_scan((long long)ncc, h->d_ccnt.p, h->d_coff.p, h->d_scan_a, s);
   for (int q = 0; q <= nclass; q++)
-    HIPCHECK(hipMemcpyAsync(h->h_coff + q, h->d_coff.p + (size_t)q * ncell, sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(h->h_coff.p + q, h->d_coff.p + (size_t)q * ncell, sizeof(long long), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));  // (also: `relabel` is a stack vector)
   h->color_off.assign((size_t)ncolors + 1, 0);
   h->color_sub.assign((size_t)nclass + 1, 0);
   h->color_nsub = nsub;
-  for (int q = 0; q <= nclass; q++) h->color_sub[q] = (int)h->h_coff[q];
-  for (int q = 0; q <= ncolors; q++) h->color_off[q] = (int)h->h_coff[nsub * q];
+  for (int q = 0; q <= nclass; q++) h->color_sub[q] = (int)h->h_coff.p[q];
+  for (int q = 0; q <= ncolors; q++) h->color_off[q] = (int)h->h_coff.p[nsub * q];
   const int tot = h->color_off[ncolors];
   h->d_rows_orig.ensure((size_t)tot + 1); h->d_rows.ensure((size_t)tot + 1);
   k_color_fill<<<nblk(ncell, 128), 128, 0, s>>>(ncell, nclass, h->d_cell_first.p, h->d_cell_fill.p, h->d_color_s.p, h->d_perm.p, h->d_coff.p,
@@ -275,9 +271,9 @@ void build_colors_distributed(polar_handle *h, bool ranked, ColorComm &cc) {
     cc.exchange(h->d_color_s.p);     // halo rows take their owners' colours (collective: every rank, every turn)
   }
   (void)color_stats(h, ranked);      // own rows -> h_cstat
-  cc.allreduce(h->h_cstat, 128);     // -> rows and rank sums per colour over all ranks
+  cc.allreduce(h->h_cstat.p, 128);     // -> rows and rank sums per colour over all ranks
   int ncolors = 0;
-  for (int c = 0; c < 64; c++) if (h->h_cstat[2 * c] > 0.0) ncolors = c + 1;
+  for (int c = 0; c < 64; c++) if (h->h_cstat.p[2 * c] > 0.0) ncolors = c + 1;
   color_finish(h, ranked, ncolors);
   h->colors_global = true;
   h->ms_color_host = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -289,17 +285,13 @@ void apply_imposed_colors(polar_handle *h) {
   const int n = h->nlocal;
   hipStream_t s = h->stream;
   if ((int)h->user_colors.size() != n) throw std::logic_error("imposed colours: atom count changed");
-  if (!h->h_cflags) {
-    HIPCHECK(hipHostMalloc((void **)&h->h_cflags, 96 * sizeof(int)));
-    HIPCHECK(hipHostMalloc((void **)&h->h_cstat, 128 * sizeof(double)));
-    HIPCHECK(hipHostMalloc((void **)&h->h_coff, POLAR_MAX_CLASS_OFF * sizeof(long long)));
-  }
+  h->h_cflags.ensure(96); h->h_cstat.ensure(128); h->h_coff.ensure(POLAR_MAX_CLASS_OFF);
   h->d_color_s.ensure(n + 1); h->d_color_orig.ensure(n + 1); h->d_cstat.ensure(128); h->d_crelabel.ensure(64);
   HIPCHECK(hipMemcpyAsync(h->d_color_orig.p, h->user_colors.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
   k_color_map<<<nblk(n, 256), 256, 0, s>>>(n, h->d_perm.p, h->d_color_orig.p, h->d_color_s.p);
   int ncolors = 0;
   for (int c : h->user_colors) ncolors = std::max(ncolors, c + 1);
-  for (int c = 0; c < 64; c++) { h->h_cstat[2 * c] = (double)(64 - c); h->h_cstat[2 * c + 1] = (double)(64 - c); }   // identity relabel: keep the caller's order
+  for (int c = 0; c < 64; c++) { h->h_cstat.p[2 * c] = (double)(64 - c); h->h_cstat.p[2 * c + 1] = (double)(64 - c); }   // identity relabel: keep the caller's order
   color_finish(h, false, ncolors);
   h->colors_global = true;
 }

@@ -97,14 +97,14 @@ struct polar_dist {
   std::vector<int> h_send_idx, h_recv_idx;      // host copies (re-sorted by colour after every colouring)
   DBuf<int> d_send_idx, d_recv_idx;
   DBuf<double> d_send, d_recv, d_red;           // packed dipoles; d_red: [0] this rank's sum (dmu)^2 -> all-reduced, [1] +inf, [2..] agreement flags and end-of-step sums
-  double *h_red = nullptr;                      // pinned
+  PinBuf<double> h_red;
   int reduce_every = 1, check_every = 4;
   int exchanges = 0, allreduces = 0, phase_exchanges = 0;   // of the last step (diagnostics)
   // schedule
   int lag = 1;                                  // phases a halo dipole may be late (0, 1, 2); -1: one exchange per sweep
   int my_class = -1, nclasses = 0;              // turn of this rank in a distributed colouring (no two peers share a class); -1: each rank colours for itself
-  hipStream_t xs = nullptr;                     // communication stream
-  hipEvent_t ev_phase[kRing] = {}, ev_xdone[kRing] = {};
+  Stream xs;                                    // communication stream
+  Event ev_phase[kRing], ev_xdone[kRing];
   // the plan by colour (valid for colouring `plan_epoch` of the handle): per colour c and peer k the atoms
   // [coff[c * np + k], coff[c * np + k + 1]) of the colour-sorted lists
   long long plan_epoch = -1;
@@ -120,15 +120,18 @@ struct polar_dist {
   // polar_dist_profile: timed events between the parts of the sweep loop; the interval that ENDS at mark k belongs to part prof_kind[k]
   double timeout_s = 180.0;        // POLAR_DIST_TIMEOUT_S: how long a wait for the device may see no progress before the step gives up (a peer that is not answering)
   bool prof_on = false;
-  std::vector<hipEvent_t> prof_ev; std::vector<int> prof_kind; size_t prof_n = 0;
+  std::vector<Event> prof_ev; std::vector<int> prof_kind; size_t prof_n = 0;
   double prof_ms[POLAR_DIST_PROF_PARTS] = {0, 0, 0, 0, 0}; int prof_intervals = 0;
+  // the members free themselves, once the communication stream has drained (the communicators: polar_dist_destroy)
+  void drain() { (void)hipSetDevice(device); if (xs) (void)hipStreamSynchronize(xs); }
+  ~polar_dist() { drain(); }
 };
 
 namespace {
 enum { PK_OTHER = 0, PK_SWEEP, PK_REDUCE, PK_XCHG, PK_ACCEL };
 inline void prof_mark(polar_dist *d, hipStream_t s, int kind) {
   if (!d->prof_on) return;
-  if (d->prof_n == d->prof_ev.size()) { hipEvent_t e; HIPCHECK(hipEventCreate(&e)); d->prof_ev.push_back(e); d->prof_kind.push_back(0); }
+  if (d->prof_n == d->prof_ev.size()) { Event e; e.create(); d->prof_ev.push_back(std::move(e)); d->prof_kind.push_back(0); }
   d->prof_kind[d->prof_n] = kind;
   HIPCHECK(hipEventRecord(d->prof_ev[d->prof_n++], s));
 }
@@ -229,7 +232,7 @@ void dist_exchange_color(polar_dist *d, polar_handle *h, int c, hipStream_t s) {
 void host_allreduce(polar_dist *d, polar_handle *h, double *vals, int count, ncclRedOp_t op) {
   if (count > 24) throw std::logic_error("host_allreduce: at most 24 doubles at a time");
   hipStream_t s = h->stream;
-  double *hr = d->h_red + 32;   // (its own pinned slots: d->h_red[0..31] belong to the end-of-step sums)
+  double *hr = d->h_red.p + 32;   // (its own pinned slots: d->h_red[0..31] belong to the end-of-step sums)
   memcpy(hr, vals, count * sizeof(double));
   HIPCHECK(hipMemcpyAsync(d->d_red.p + 32, hr, count * sizeof(double), hipMemcpyHostToDevice, s));
   RCCLCHECK(rccl().AllReduce(d->d_red.p + 32, d->d_red.p + 32, count, ncclDouble, op, d->comm, s));
@@ -342,12 +345,12 @@ int polar_dist_create(const void *id128, int rank, int nranks, int device, polar
       if (rccl().CommSplit(d->comm, 0, rank, &second, nullptr) == ncclSuccess && second) d->comm_red = second;   // (collective; on failure: one communicator)
     }
     d->d_red.ensure(128);
-    HIPCHECK(hipHostMalloc((void **)&d->h_red, 128 * sizeof(double)));
+    d->h_red.ensure(128);
     const double inf = INFINITY;
     HIPCHECK(hipMemcpy(d->d_red.p + 1, &inf, sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(hipStreamCreateWithFlags(&d->xs, hipStreamNonBlocking));
-    for (auto &e : d->ev_phase) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (auto &e : d->ev_xdone) HIPCHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    d->xs.create(hipStreamNonBlocking);
+    for (auto &e : d->ev_phase) e.create(hipEventDisableTiming);
+    for (auto &e : d->ev_xdone) e.create(hipEventDisableTiming);
     if (const char *e = getenv("POLAR_DIST_LAG")) d->lag = std::max(-1, std::min(2, atoi(e)));
     if (const char *e = getenv("POLAR_DIST_TIMEOUT_S")) d->timeout_s = std::max(1.0, atof(e));
     return (int)POLAR_OK;
@@ -355,18 +358,10 @@ int polar_dist_create(const void *id128, int rank, int nranks, int device, polar
 }
 int polar_dist_destroy(polar_dist *d) {
   if (!d) return POLAR_OK;
-  (void)hipSetDevice(d->device);
-  if (d->xs) (void)hipStreamSynchronize(d->xs);
+  d->drain();   // (the communicators are idle before they go)
   if (d->comm_red && d->comm_red != d->comm) { try { (void)rccl().CommDestroy(d->comm_red); } catch (const std::exception &) {} }
   if (d->comm) { try { (void)rccl().CommDestroy(d->comm); } catch (const std::exception &) {} }
-  for (auto &e : d->ev_phase) if (e) (void)hipEventDestroy(e);
-  for (auto &e : d->ev_xdone) if (e) (void)hipEventDestroy(e);
-  for (auto &e : d->prof_ev) if (e) (void)hipEventDestroy(e);
-  if (d->xs) (void)hipStreamDestroy(d->xs);
-  d->d_send_idx.release(); d->d_recv_idx.release(); d->d_send.release(); d->d_recv.release(); d->d_red.release();
-  d->d_csend_idx.release(); d->d_crecv_idx.release(); d->d_csend.release(); d->d_crecv.release(); d->d_gowner.release(); d->d_gshift.release();
-  if (d->h_red) (void)hipHostFree(d->h_red);
-  delete d;
+  delete d;   // (the members free themselves)
   return POLAR_OK;
 }
 const char *polar_dist_last_error(const polar_dist *d) { return d ? d->err.c_str() : "null driver"; }
@@ -593,7 +588,7 @@ int polar_dist_step(polar_dist *d, polar_handle *h, int eflag, int vflag, polar_
           if (!st.fixed_iteration && look_at_state(h, sw, d->check_every, d->reduce_every)) {
             dist_wait(d, s);
             read_scal(h);  // identical on every rank: same all-reduced sum (sweeps past the end are no-ops on the device)
-            if (h->h_scal->done) break;
+            if (h->h_scal.p->done) break;
           }
         }
         if (g > 0) HIPCHECK(hipStreamWaitEvent(s, d->ev_xdone[(g - 1) % kRing], 0));   // every halo dipole is its owner's final one
@@ -658,7 +653,7 @@ int polar_dist_step(polar_dist *d, polar_handle *h, int eflag, int vflag, polar_
           if (!st.fixed_iteration && look_at_state(h, sw, d->check_every, d->reduce_every)) {
             dist_wait(d, s);
             read_scal(h);  // identical on every rank: same all-reduced sum (sweeps past the end are no-ops on the device)
-            if (h->h_scal->done) break;
+            if (h->h_scal.p->done) break;
             prof_mark(d, s, PK_OTHER);
           }
         }
@@ -681,7 +676,7 @@ int polar_dist_step(polar_dist *d, polar_handle *h, int eflag, int vflag, polar_
       d->local = *out;
       // a rank whose rows outgrew their pitch reports POLAR_RETRY_STEP: the flag is max-reduced so that all ranks repeat
       // together; the same call sums energies, virial and pair counts over the ranks
-      double *hr = d->h_red;
+      double *hr = d->h_red.p;
       hr[0] = rc == POLAR_RETRY_STEP ? 1.0 : 0.0;
       hr[1] = out->eng_vdwl; hr[2] = out->eng_coul; hr[3] = out->eng_pol; hr[4] = out->u_self; hr[5] = out->u_ef; hr[6] = out->u_dd;
       for (int k = 0; k < 6; k++) hr[7 + k] = out->virial[k];

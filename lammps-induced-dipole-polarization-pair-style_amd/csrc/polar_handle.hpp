@@ -6,7 +6,12 @@
 //                    solve (PS.cpp:1113-1238), forces; the sweep launchers
 //   polar_color.hip  colour phases of the list-mode Gauss-Seidel (device colouring, re-validation)
 //   polar_dist.hip   multi-GPU driver over RCCL (polar_dist_*)
-// polar_plan.hpp (plain C++, tested on the host) holds the arithmetic that lays a step out: grid, pitches, k-vectors, nblk.
+// polar_plan.hpp (plain C++, tested on the host) holds the arithmetic that lays a step out: grid, pitches, k-vectors, nblk;
+// polar_input.hpp (the same) what the entry points decide about their inputs: position scan, table analysis and packing, the
+// grid of polar_build_neighbors, the solver rule, the restart record.
+// polar_own.hpp holds the owners (DBuf, PinBuf, Event, Stream) with HipError and HIPCHECK.  Every device buffer, pinned buffer,
+// event and stream of the handle is a member of one of these types and frees itself: a new one is declared here and nowhere
+// else, polar_destroy is `delete h`, and ~polar_handle only waits for the streams before the members go.
 // No CPU implementation of the hot path anywhere: without a GPU every compute call fails.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,6 +37,8 @@
 #include <vector>
 
 #include "pair_host.hpp"
+#include "polar_input.hpp"
+#include "polar_own.hpp"
 #include "polar_kernels.hpp"
 #include "polar_plan.hpp"
 
@@ -42,45 +49,9 @@ using namespace polar;
 #define POLAR_MAX_CLASS_OFF 130   // phase classes of a colouring + 1: up to 64 colours, each split into boundary / interior rows on a sharded handle
 
 
-struct HipError : std::runtime_error {
-  explicit HipError(const std::string &m) : std::runtime_error(m) {}
-};
 struct NoDevice : std::runtime_error {
   NoDevice() : std::runtime_error("no usable HIP device: this library has no CPU fallback") {}
 };
-#define HIPCHECK(expr)                                                                             \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess)                                                                          \
-      throw HipError(std::string(#expr) + " failed: " + hipGetErrorString(e_) + " (" + __FILE__ + \
-                     ":" + std::to_string(__LINE__) + ")");                                      \
-  } while (0)
-
-template <typename T>
-struct DBuf {
-  T *p = nullptr;
-  size_t cap = 0;
-  void ensure(size_t n) {
-    if (n <= cap) return;
-    if (p) HIPCHECK(hipFree(p));
-    size_t want = n + n / 8 + 64;
-    HIPCHECK(hipMalloc((void **)&p, want * sizeof(T)));
-    cap = want;
-    // POLAR_POISON=1 (debugging aid): a fresh process gets zero pages from hipMalloc, a long-lived one gets recycled memory --
-    // fill every new buffer with 0x7F bytes (ints 2139062143, doubles 1.4e306) so that a read-before-write shows in the FIRST
-    // call of a process instead of the ninetieth (the abort of round 4)
-    static const bool poison = getenv("POLAR_POISON") && atoi(getenv("POLAR_POISON")) != 0;
-    if (poison) {   // (the fill runs on the null stream, which the library's non-blocking streams do not wait for: finish it here)
-      HIPCHECK(hipMemset(p, 0x7F, want * sizeof(T)));
-      HIPCHECK(hipDeviceSynchronize());
-    }
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-  }
-};
-
 // one launch zeroing up to six small device buffers (sizes in bytes, multiples of 4)
 inline void zero_many(hipStream_t s, std::initializer_list<std::pair<void *, size_t>> bufs) {
   ZeroJobs jobs;
@@ -116,7 +87,8 @@ inline double min_image_dist2(const Box &b, const double *xi, const double *xj) 
 struct polar_handle {
   int device = -1;
   bool have_device = false;
-  hipStream_t stream = nullptr;
+  bool device_set = false;   // hipSetDevice(device) has succeeded: there may be something on the device to wait for and to free
+  Stream stream;             // the main stream; polar_set_stream lends the caller's (Stream::borrow)
   std::string err, warn;
   PairHost ph;
   bool types_set = false, coul_set = false, box_set = false, atoms_set = false, neigh_set = false;
@@ -131,7 +103,6 @@ struct polar_handle {
   int newton_pair = 1;           // force->newton_pair of the uploaded half list (polar_set_newton)
   int step_eflag = 0, step_vflag = 0;
   bool in_step = false;
-  bool own_stream = true;
   // host mirrors needed by host-side colouring
   std::vector<double> hx, halpha;
   // device state
@@ -189,8 +160,8 @@ struct polar_handle {
   long long nl_pitch = 0, dd_pitch = 0;   // pitched row lists (see polar_kernels.hpp RowList)
   DBuf<int> d_overflow;
   DBuf<unsigned long long> d_ddtot;
-  int *h_flags = nullptr;                   // pinned: [0] overflow (needed count), [1..] unused
-  unsigned long long *h_ddtot = nullptr;    // pinned: 64 x 16 partial totals
+  PinBuf<int> h_flags;                      // pinned: [0] overflow (needed count), [1..] unused
+  PinBuf<unsigned long long> h_ddtot;       // pinned: 64 x 16 partial totals
   int inum = 0;
   long long nneigh = 0;
   bool mu_resident = false;
@@ -210,8 +181,8 @@ struct polar_handle {
   DBuf<int> d_bflag; int bflag_n = 0;   // multi-GPU: sub-class by original index (polar_dist_set_halo: 0 = a peer receives this row's dipole, 1 = not), bflag_n = atoms it was made for
   // the neighbor list's upload: its own stream, one pinned buffer (+ event) per 32-MB chunk, host copies of the row tables that
   // must outlive the call, the event its consumers wait for
-  std::vector<int *> h_nl_stage; std::vector<hipEvent_t> ev_nl;
-  hipStream_t up_stream = nullptr; hipEvent_t ev_list_up = nullptr; bool list_up_pending = false;
+  std::vector<PinBuf<int>> h_nl_stage; std::vector<Event> ev_nl;
+  Stream up_stream; Event ev_list_up; bool list_up_pending = false;
   std::vector<long long> h_first; std::vector<int> h_nn, h_ilist;
   bool colors_global = false;  // the colouring in force is consistent across the ranks of a multi-GPU run (halo rows carry their owners' colours)
   std::vector<int> user_colors;  // polar_set_colors: a colouring imposed by the caller (original order, -1 = none)
@@ -231,9 +202,9 @@ struct polar_handle {
   DBuf<unsigned long long> d_cprio;
   DBuf<double> d_cstat;
   DBuf<long long> d_coff;
-  int *h_cflags = nullptr;        // pinned: round counters / fold counters of the device colouring
-  double *h_cstat = nullptr;      // pinned: rows and rank sums per colour
-  long long *h_coff = nullptr;    // pinned: first row of every phase class (POLAR_MAX_CLASS_OFF entries: 64 colours x 2 sub-classes + 1)
+  PinBuf<int> h_cflags;           // pinned: round counters / fold counters of the device colouring
+  PinBuf<double> h_cstat;         // pinned: rows and rank sums per colour
+  PinBuf<long long> h_coff;       // pinned: first row of every phase class (POLAR_MAX_CLASS_OFF entries: 64 colours x 2 sub-classes + 1)
   int cadj_pitch = 16;            // conflict-list entries per atom (grown when an atom has more neighbours within the colour distance)
   int host_colors = 0;            // lab (POLAR_HOST_COLORS): rounds 1-2's host-side conflict graph + DSATUR instead of the device colouring
   int colors_reused = 0, colors_rebuilt = 0;
@@ -304,22 +275,22 @@ struct polar_handle {
   int tile_wide = 0;               // cells of a whole cutoff in x (tiles of ~30 rows) instead of half a cutoff (~15) (POLAR_TILE_WIDE)
   int tile_sw[3] = {2, 2, 2};      // stencil half-widths of the tile builder, in cells
   int deterministic = 0;           // POLAR_DETERMINISTIC / `deterministic yes`: no sweep reads a dipole another wave of the same launch writes
-  Scal *h_scal = nullptr;  // pinned
-  hipEvent_t ev[8] = {};
+  PinBuf<Scal> h_scal;
+  Event ev[8];
   // a3 runs on its own stream beside the list build / static field / dipole solve (it only shares the
   // force and tally accumulators with them): fork after the accumulators are zeroed, join before they are read
-  hipStream_t lj_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_lj0 = nullptr, ev_lj1 = nullptr, ev_dl0 = nullptr, ev_dl1 = nullptr;
+  Stream lj_stream;
+  Event ev_fork, ev_join, ev_lj0, ev_lj1, ev_dl0, ev_dl1;
   // polar_compute: the dipoles and the static field are final before the force kernel starts; they travel to the host on
   // their own stream while it runs (early_mu / early_ef: where in the pinned staging area; null = not asked for)
-  hipStream_t dl_stream = nullptr;
-  hipEvent_t ev_mu_ready = nullptr;
+  Stream dl_stream;
+  Event ev_mu_ready;
   double *early_mu = nullptr, *early_ef = nullptr, *user_mu = nullptr, *user_ef = nullptr;  // staging slots; the caller's arrays
-  hipEvent_t ev_fchunk[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event ev_fchunk[4];
   bool overlap_lj = true;  // POLAR_NO_OVERLAP=1 keeps a3 on the main stream
   bool lj_forked = false;
   std::vector<double> h_tmp;
-  double *h_stage = nullptr;  // pinned staging area for downloads
+  PinBuf<double> h_stage;     // pinned staging area for downloads (staging())
   DBuf<double> d_trace;       // `debug yes`: u_polar after every sweep of the last solve
   // `polar_ewald` (polar_ewald.hpp): the k-vector set of the last box / g_ewald / accuracy (rebuilt when one of them changes),
   // structure factors S and M, chunk partials, the reciprocal field (s space), workgroup partials, [u_ef, virial[6]]
@@ -329,9 +300,17 @@ struct polar_handle {
   std::vector<double> ew_key;
   int ew_nk = 0, ew_nrow = 0, ew_nm = 0;
   double ew_cell[6] = {0, 0, 0, 0, 0, 0};
-  hipEvent_t ev_ks[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event ev_ks[4];
   int ntrace = 0;
-  size_t h_stage_cap = 0;
+  // Everything above frees itself.  What is left to do first: let the device finish with it.
+  ~polar_handle() {
+    if (!device_set) return;
+    (void)hipSetDevice(device);
+    for (hipStream_t s : {(hipStream_t)stream, (hipStream_t)lj_stream, (hipStream_t)up_stream, (hipStream_t)dl_stream})
+      if (s) (void)hipStreamSynchronize(s);
+  }
+  // the settings changed: the colour phases and every list pitch are made again
+  void reset_plan() { colors_valid = false; nl_pitch = dd_pitch = 0; cl_pitch = 0; un_pitch = 0; pitch16 = 0; }
 };
 inline int fail(polar_handle *h, int code, const std::string &m) {
   if (h) h->err = m;
@@ -358,18 +337,15 @@ int guarded(polar_handle *h, F &&fn) {
 
 // pinned host staging area of at least `count` doubles (grown geometrically, freed with the handle)
 inline double *staging(polar_handle *h, size_t count) {
-  if (count > h->h_stage_cap) {
-    if (h->h_stage) {  // (an upload or an early download may still be using the old area)
+  if (count > h->h_stage.cap) {
+    if (h->h_stage.p) {  // (an upload or an early download may still be using the old area)
       if (h->stream) (void)hipStreamSynchronize(h->stream);
       if (h->dl_stream) (void)hipStreamSynchronize(h->dl_stream);
-      (void)hipHostFree(h->h_stage);
     }
-    h->h_stage = nullptr; h->h_stage_cap = 0;
-    const size_t want = count + count / 4 + 1024;
-    HIPCHECK(hipHostMalloc((void **)&h->h_stage, want * sizeof(double)));
-    h->h_stage_cap = want;
+    h->h_stage.release();
+    h->h_stage.ensure(count + count / 4 + 1024);
   }
-  return h->h_stage;
+  return h->h_stage.p;
 }
 
 inline void need_device(polar_handle *h) {

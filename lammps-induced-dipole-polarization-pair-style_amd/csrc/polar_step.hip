@@ -179,8 +179,8 @@ void build_lists(polar_handle *h) {
     k_dd_scalars<1><<<nblk(nr, POLAR_ROWS_PER_BLOCK), POLAR_BLOCK, 0, s>>>(rows, nr, h->d_rec0.p, h->box, ddl, h->d_dd_j.p, st.polar_damp, sp, r2p);
 #endif
   // overflow flag and dd total come back with the end-of-step read (no sync here)
-  HIPCHECK(hipMemcpyAsync(h->h_flags, h->d_overflow.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipMemcpyAsync(h->h_ddtot, h->d_ddtot.p, 64 * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(h->h_flags.p, h->d_overflow.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(h->h_ddtot.p, h->d_ddtot.p, 64 * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
 }
 template <bool AP>
 static void launch_rank(polar_handle *h, int pass) {
@@ -503,7 +503,7 @@ void ewald_forces(polar_handle *h) {
 
 void read_scal(polar_handle *h) {
   HIPCHECK(hipGetLastError());  // a failed kernel launch must not go unnoticed
-  HIPCHECK(hipMemcpyAsync(h->h_scal, h->d_scal.p, sizeof(Scal), hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->h_scal.p, h->d_scal.p, sizeof(Scal), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
 }
 #ifdef POLAR_LAB
@@ -592,7 +592,7 @@ static void launch_accel_mix(polar_handle *h, int tot, int nb) {
 static bool sweep_stops(polar_handle *h, int sw, int check_every) {
   if (h->ph.st.fixed_iteration || !look_at_state(h, sw, check_every)) return false;
   read_scal(h);
-  return h->h_scal->done != 0;
+  return h->h_scal.p->done != 0;
 }
 
 void solve(polar_handle *h, bool ap, polar_result *out) {
@@ -1006,7 +1006,7 @@ int phase_finish(polar_handle *h, polar_result *out) {
   h->mu_resident = true;
   h->mu_host_in_sync = false;  // d_mu has new numbers; polar_compute / polar_compute_peratom set this again once the caller's array holds them
 
-  const Scal &sc = *h->h_scal;
+  const Scal &sc = *h->h_scal.p;
   out->eng_vdwl = sc.eng_vdwl; out->eng_coul = sc.eng_coul;
   out->u_self = sc.u_self; out->u_ef = sc.u_ef; out->u_dd = sc.u_dd;
   out->eng_pol = sc.u_self + sc.u_ef + sc.u_dd;  // PS.cpp:632 (all zero when eflag == 0)
@@ -1031,7 +1031,7 @@ int phase_finish(polar_handle *h, polar_result *out) {
   h->last_sweeps = (!st.fixed_iteration && !st.zodid && !sc.status && sc.done) ? sc.sweeps : 0;   // (where the next solve's first look at the loop state goes)
   if (!ap) {
     unsigned long long tot = 0;
-    for (int k = 0; k < 64; k++) tot += h->h_ddtot[16 * k];
+    for (int k = 0; k < 64; k++) tot += h->h_ddtot.p[16 * k];
     h->dd_pairs = (long long)tot;
   }
   out->dd_pairs = ap ? (long long)n * (n - 1) : h->dd_pairs;
@@ -1049,7 +1049,7 @@ int phase_finish(polar_handle *h, polar_result *out) {
 
 // end-of-step flags of the pitched lists (pinned, copied at the end of the list builds): true = a list did not fit, the
 // pitches have been enlarged and the step must be repeated
-void clear_flags(polar_handle *h) { for (int k = 0; k < 16; k++) h->h_flags[k] = 0; }
+void clear_flags(polar_handle *h) { for (int k = 0; k < 16; k++) h->h_flags.p[k] = 0; }
 void tile_fallback(polar_handle *h) {
   h->sweep_kernel = 2;
   h->colors_valid = false; h->slots_by_color = false;
@@ -1058,22 +1058,22 @@ void tile_fallback(polar_handle *h) {
 }
 bool grow_pitches(polar_handle *h) {
   bool again = false;
-  if (h->h_flags[0] != 0) {
-    h->nl_pitch = h->dd_pitch = std::max(pitch_grown(h->h_flags[0]), h->nl_pitch + 64);
+  if (h->h_flags.p[0] != 0) {
+    h->nl_pitch = h->dd_pitch = std::max(pitch_grown(h->h_flags.p[0]), h->nl_pitch + 64);
     again = true;
   }
-  if (h->h_flags[4] != 0) { h->cl_pitch = (((long long)(1.25 * h->h_flags[4]) + 255) / 256) * 256; again = true; }
+  if (h->h_flags.p[4] != 0) { h->cl_pitch = (((long long)(1.25 * h->h_flags.p[4]) + 255) / 256) * 256; again = true; }
   if (h->sweep_kernel == 4) {
-    if (h->h_flags[7] != 0) { tile_fallback(h); return true; }
-    if (h->h_flags[5] != 0) {  // a union list beyond the pitch, or beyond what the sweep's LDS request holds
-      const int need = (int)(((long long)(1.15 * h->h_flags[5]) + 16 + 63) / 64 * 64);
+    if (h->h_flags.p[7] != 0) { tile_fallback(h); return true; }
+    if (h->h_flags.p[5] != 0) {  // a union list beyond the pitch, or beyond what the sweep's LDS request holds
+      const int need = (int)(((long long)(1.15 * h->h_flags.p[5]) + 16 + 63) / 64 * 64);
       if (need > tile_lds_cap()) { tile_fallback(h); return true; }
       h->un_pitch = std::max(h->un_pitch, need); h->un_lds = h->un_pitch;
       again = true;
     }
-    if (h->h_flags[6] != 0) { h->pitch16 = ((long long)(1.25 * h->h_flags[6]) + 511) / 512 * 512; again = true; }
-    if (!again && h->h_flags[9] > 0) {  // next step: ask only for the LDS the unions need (two workgroups per CU below 80 KB)
-      h->tile_max_u = h->h_flags[9];
+    if (h->h_flags.p[6] != 0) { h->pitch16 = ((long long)(1.25 * h->h_flags.p[6]) + 511) / 512 * 512; again = true; }
+    if (!again && h->h_flags.p[9] > 0) {  // next step: ask only for the LDS the unions need (two workgroups per CU below 80 KB)
+      h->tile_max_u = h->h_flags.p[9];
       h->un_lds = std::min(h->un_pitch, (int)((long long)(1.06 * (h->tile_max_u + 1)) + 8 + 7) / 8 * 8);
       if (getenv("POLAR_DEBUG") && !h->tile_reported) {
         h->tile_reported = true;

@@ -105,3 +105,23 @@ def test_product_translation_units_never_include_lab_code():
         blob = open(so, "rb").read()
         for name in (b"k_field_tile", b"k_field_quad", b"k_field_lpr", b"k_field_lp2", b"k_field_cl", b"k_region_sub", b"POLAR_ABLATE", b"POLAR_PIPELINE"):
             assert name not in blob, name
+
+
+def test_only_the_owners_give_resources_back():
+    """Device and pinned memory, events and streams are freed by the owners of csrc/polar_own.hpp and by nobody else: no line of
+    a translation unit, of the handle's header or of csrc/lab/ calls the runtime's free / destroy functions itself (a buffer
+    let go early goes through its owner's release())."""
+    calls = re.compile(r"\b(hipFree|hipHostFree|hipEventDestroy|hipStreamDestroy)\b")
+    lab = os.path.join(CSRC, "lab")
+    files = SRCS + [os.path.join(CSRC, "polar_handle.hpp")] + [os.path.join(lab, f) for f in sorted(os.listdir(lab))]
+    for path in files:
+        with open(path) as fh:
+            hits = [(k + 1, ln.strip()) for k, ln in enumerate(fh) if calls.search(ln)]
+        assert hits == [], (os.path.relpath(path, CSRC), hits)
+    callers = set()
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith((".hip", ".hpp", ".inc")):
+            with open(os.path.join(CSRC, f)) as fh:
+                if calls.search(fh.read()):
+                    callers.add(f)
+    assert callers == {"polar_own.hpp"}, callers

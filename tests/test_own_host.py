@@ -1,0 +1,102 @@
+"""The owners of the library's HIP resources (csrc/polar_own.hpp: DBuf, PinBuf, Event, Stream) on the host.
+
+The header needs the runtime API's declarations and nothing else: g++ builds tests/own/own_host.cpp around it and links
+tests/own/fake_hip.cpp, a stand-in for the fourteen runtime calls over malloc that counts what is live -- a stand-alone
+program (with the address and undefined-behaviour sanitizers where the toolchain has them) that reads commands on stdin.
+Nothing is loaded into Python and no GPU is needed.  A double free, a use after release or a block never freed ends the
+program with the sanitizer's report; the live counts have to say the same."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "lammps-induced-dipole-polarization-pair-style_amd")
+SRC = [os.path.join(ROOT, "tests", "own", f) for f in ("own_host.cpp", "fake_hip.cpp")]
+HIP_INCLUDE = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "include")
+NONE = ["0", "0", "0", "0"]
+
+
+@pytest.fixture(scope="module")
+def own(tmp_path_factory):
+    if not os.path.exists(os.path.join(HIP_INCLUDE, "hip", "hip_runtime_api.h")):
+        pytest.skip("no HIP runtime headers")
+    exe = str(tmp_path_factory.mktemp("own") / "own_host")
+    base = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-D__HIP_PLATFORM_AMD__", f"-I{PKG}/csrc",
+            "-isystem", HIP_INCLUDE, "-o", exe] + SRC
+    r = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True)
+    if r.returncode != 0 and "sanitize" in r.stderr:      # a toolchain without the sanitizer runtimes: the plain program
+        r = subprocess.run(base, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+
+    def run(*commands, env=None):
+        """One list of output tokens per command; the program itself ends non-zero if anything is still live."""
+        text = "".join(" ".join(str(v) for v in c) + "\n" for c in commands)
+        e = dict(os.environ)
+        e.pop("POLAR_POISON", None)
+        e.update(env or {})
+        p = subprocess.run([exe], input=text, capture_output=True, text=True, env=e)
+        assert p.returncode == 0, (p.returncode, p.stdout[-1000:], p.stderr[-3000:])
+        return [ln.split() for ln in p.stdout.splitlines()]
+    return run
+
+
+def test_ensure_grows_to_n_plus_an_eighth_plus_64_and_keeps_what_is_large_enough(own):
+    ns = (0, 1, 64, 65, 1000000)
+    out = own(("caps", len(ns), *ns), ("live",))
+    for n, (cap, first, second, kept) in zip(ns, out):
+        assert int(cap) == (n + n // 8 + 64 if n > 0 else 0), n
+        assert int(first) == (1 if n > 0 else 0), n      # one allocation
+        assert int(second) == 0, n                       # the same n again: none
+        assert int(kept) == 1, n                         # nor for anything up to cap: the same block
+    assert out[-1] == NONE
+
+
+def test_every_owner_frees_what_it_holds_at_scope_exit(own):
+    inside, after = (lambda t: (t[:4], t[4:]))(own(("scope",))[0])
+    assert inside == ["1", "1", "2", "3"]
+    assert after == NONE
+
+
+def test_release_then_scope_exit_frees_once(own):
+    released, after = (lambda t: (t[:4], t[4:]))(own(("release",))[0])
+    assert released == NONE and after == NONE
+
+
+@pytest.mark.parametrize("count", [0, 1, 70])
+def test_owners_moved_into_a_growing_vector(own, count):
+    """h_nl_stage and ev_nl grow one element at a time past the ring of 64: every reallocation moves the owners."""
+    t = own(("vector", count))[0]
+    assert t[:4] == ["0", str(count), str(count), "0"]
+    assert t[4] == "1"
+    assert t[5:] == NONE
+
+
+def test_a_moved_from_owner_is_empty(own):
+    t = own(("moves",))[0]
+    assert t[:5] == ["1"] * 5
+    assert t[5:] == NONE
+
+
+def test_a_failed_growth_leaves_the_buffer_empty(own):
+    t = own(("fail",), ("live",))
+    dbuf, pin, after = t[0][:5], t[0][5:10], t[0][10:]
+    #               thrown  p==0  cap  live  cap after the next ensure
+    assert dbuf == ["1", "1", "0", "0", str(1000 + 125 + 64)]
+    assert pin == ["1", "1", "0", "0", "1000"]
+    assert after == NONE and t[1] == NONE
+
+
+def test_a_borrowed_stream_is_never_destroyed(own):
+    t = own(("borrow",))
+    assert t[0] == ["1", "1", "0", "1", "1", "0"]
+
+
+def test_poison_fills_a_new_block(own):
+    assert own(("poison",), env={"POLAR_POISON": "1"})[0] == ["127", "127"]
+
+
+def test_program_ends_with_nothing_live(own):
+    """All commands in one run: the exit status (0 only with every count at zero) and the leak check at exit."""
+    out = own(("caps", 3, 5, 70, 9), ("scope",), ("release",), ("vector", 70), ("moves",), ("fail",), ("borrow",), ("live",))
+    assert out[-1] == NONE
