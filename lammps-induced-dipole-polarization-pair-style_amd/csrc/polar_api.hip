@@ -840,8 +840,7 @@ int polar_step_sweep_end_n(polar_handle *h, const double *dev_global_change, int
     const polar_settings &st = h->ph.st;
     const bool gs = st.polar_gs || st.polar_gs_ranked;
     if (count > 1 && !(gs && st.fixed_iteration)) throw InputError("polar_step_sweep_end_n: count > 1 needs fixed-iteration Gauss-Seidel");
-    k_solver_step<<<1, POLAR_NSLOT, 0, h->stream>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision,
-                                          gs ? 0 : 1, dev_global_change, count, det_part(h), det_npart(h));
+    launch_solver_step(h, dev_global_change, count);
     return POLAR_OK;
   });
 }

@@ -180,11 +180,7 @@ int dist_guarded(polar_dist *d, F &&fn) {
   if (!d) return POLAR_ERR_STATE;
   try {
     return fn();
-  } catch (const InputError &e) { d->err = e.what(); return POLAR_ERR_INPUT;
-  } catch (const Unsupported &e) { d->err = e.what(); return POLAR_ERR_UNSUPPORTED;
-  } catch (const NoDevice &e) { d->err = e.what(); return POLAR_ERR_NO_DEVICE;
-  } catch (const HipError &e) { d->err = e.what(); return POLAR_ERR_HIP;
-  } catch (const std::exception &e) { d->err = e.what(); return POLAR_ERR_STATE; }
+  } catch (...) { return error_code(d->err); }
 }
 // grouped send / receive with the peers: segment k of the packed buffers = peer k; `unit` doubles per atom
 void p2p(polar_dist *d, const int *soff, const int *roff, const double *sendbuf, double *recvbuf, int unit, hipStream_t s) {
@@ -311,6 +307,31 @@ void color_together(polar_dist *d, polar_handle *h) {
   h->colors_valid = false;
   build_colors_distributed(h, h->ph.st.polar_gs_ranked != 0, cc);
   map_color_rows(h);
+}
+// ---- after a sweep (polar_plan.hpp, sweep_end), both schedules -------------------------------------------------------------
+// `polar_accel m` across the ranks: every rank mixes with the SAME coefficients.  This rank's dot products leave one launch
+// (precision mode, `decide`: with its change in front), one all-reduce of 1 + 16 doubles sums them, then the coefficients and
+// the mix (`decide`: and the end-of-sweep decision on the all-reduced change, in the same launch)
+void accel_round(polar_dist *d, polar_handle *h, bool decide, hipStream_t s) {
+  double *ared = d->d_red.p + 64;   // [0] sum (dmu)^2, [1 .. 16] the dot products
+  if (decide) accel_export_fused(h, ared); else accel_export(h, ared + 1);
+  prof_mark(d, s, PK_ACCEL);
+  RCCLCHECK(rccl().AllReduce(ared, ared, 1 + 2 * POLAR_ACCEL_MAXM, ncclDouble, ncclSum, d->comm_red, s));
+  d->allreduces++;
+  prof_mark(d, s, PK_REDUCE);
+  if (decide) accel_decide_mix(h, ared, false); else accel_step(h, ared + 1);
+  prof_mark(d, s, PK_ACCEL);
+}
+// What the stop rule of precision mode (PS.cpp:1194-1210) reads after a sweep: the sum of (dmu)^2 over all ranks -- one
+// all-reduced double, this rank's partial sums folded into it first -- on a sweep that reduces, "not converged yet" (+inf)
+// beside the rank's own partial sums on the others
+struct Change { const double *gc, *part; int npart; };
+Change stop_rule_change(polar_dist *d, polar_handle *h, bool reduce, hipStream_t s) {
+  if (!reduce) return Change{d->d_red.p + 1, det_part(h), det_npart(h)};
+  k_fold_change<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, d->d_red.p, det_part(h), det_npart(h));
+  RCCLCHECK(rccl().AllReduce(d->d_red.p, d->d_red.p, 1, ncclDouble, ncclSum, d->comm_red, s));
+  d->allreduces++;
+  return Change{d->d_red.p, nullptr, 0};
 }
 }  // namespace
 
@@ -496,11 +517,7 @@ int polar_dist_step(polar_dist *d, polar_handle *h, int eflag, int vflag, polar_
           throw InputError("polar_accel across ranks needs the Gauss-Seidel sweep of list mode (polar_gs / polar_gs_ranked)");
         if (st.polar_accel > 0 && deterministic(h)) throw InputError("polar_accel and `deterministic yes` exclude each other");
         step_begin_lists(h, eflag, vflag);
-      } catch (const InputError &e) { brc = POLAR_ERR_INPUT; berr = e.what();
-      } catch (const Unsupported &e) { brc = POLAR_ERR_UNSUPPORTED; berr = e.what();
-      } catch (const NoDevice &e) { brc = POLAR_ERR_NO_DEVICE; berr = e.what();
-      } catch (const HipError &e) { brc = POLAR_ERR_HIP; berr = e.what();
-      } catch (const std::exception &e) { brc = POLAR_ERR_STATE; berr = e.what(); }
+      } catch (...) { brc = error_code(berr); }
       const bool shared = d->my_class >= 0 && gs && !st.zodid && h->sweep_kernel == 2;
       // (the same all-reduce makes the ranks agree on WHERE they look at the loop state -- look_at_state works from the sweep count
       //  of the handle's last solve, and ranks that looked at different sweeps would leave the loop at different sweeps: one of
@@ -530,12 +547,9 @@ int polar_dist_step(polar_dist *d, polar_handle *h, int eflag, int vflag, polar_
       try {
       if (!st.zodid && phased) {
         const int nc = d->plan_nc, lag = deterministic(h) ? 0 : d->lag;
-        const bool lazy = st.fixed_iteration != 0;
-        // `polar_accel m` across the ranks: every rank mixes with the SAME coefficients -- the dot products ride the stop
-        // rule's all-reduce (1 + 16 doubles, every sweep) -- and the mixed boundary dipoles travel in one exchange of all
-        // halo rows after the mix (every row changed, not one colour)
+        // `polar_accel m` across the ranks (accel_round): the mixed boundary dipoles travel in one exchange of all halo rows
+        // after the mix (every row changed, not one colour)
         const bool accel = accel_begin(h, false);
-        double *ared = d->d_red.p + 64;   // [0] sum (dmu)^2, [1 .. 16] the dot products
         // boundary rows first, the exchange behind the interior rows -- where there are interior rows worth a launch of their
         // own (8 slabs two cutoffs thick have none: every row is some peer's halo)
         long long interior = 0, rows = h->color_off.empty() ? 0 : h->color_off.back();
@@ -556,36 +570,20 @@ int polar_dist_step(polar_dist *d, polar_handle *h, int eflag, int vflag, polar_
             dist_exchange_color(d, h, c, d->xs);
             HIPCHECK(hipEventRecord(d->ev_xdone[g % kRing], d->xs));
           }
-          if (accel && (!lazy || sw < max_sweeps - 1)) {
+          const SweepEnd e = sweep_end(sw, max_sweeps, st.fixed_iteration != 0, gs, accel, d->reduce_every);
+          if (e.mix) {
             if (g > 0) HIPCHECK(hipStreamWaitEvent(s, d->ev_xdone[(g - 1) % kRing], 0));   // no late unpack may land on the mixed dipoles
             prof_mark(d, s, PK_OTHER);
-            if (lazy) accel_export(h, ared + 1); else accel_export_fused(h, ared);   // (precision mode: the rank's change and its dot products leave one launch)
-            prof_mark(d, s, PK_ACCEL);
-            RCCLCHECK(R.AllReduce(ared, ared, 1 + 2 * POLAR_ACCEL_MAXM, ncclDouble, ncclSum, d->comm_red, s));
-            d->allreduces++;
-            prof_mark(d, s, PK_REDUCE);
-            if (lazy) accel_step(h, ared + 1); else accel_decide_mix(h, ared, false);   // (the decision on the all-reduced change and the coefficients: one launch)
-            prof_mark(d, s, PK_ACCEL);
+            accel_round(d, h, e.decide_in_mix, s);
             dist_exchange(d, h);
             prof_mark(d, s, PK_XCHG);
-          } else if (!st.fixed_iteration) {
-            const double *gc = d->d_red.p + 1;   // +inf: "not converged yet"
-            if ((sw % d->reduce_every) == d->reduce_every - 1 || sw >= st.iterations_max) {
-              k_fold_change<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, d->d_red.p, det_part(h), det_npart(h));
-              RCCLCHECK(R.AllReduce(d->d_red.p, d->d_red.p, 1, ncclDouble, ncclSum, d->comm_red, s));
-              d->allreduces++;
-              gc = d->d_red.p;
-            }
-            k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision,
-                                                  0, gc, 1, gc == d->d_red.p ? nullptr : det_part(h), gc == d->d_red.p ? 0 : det_npart(h));
+          }
+          if (e.count > 0 && !st.fixed_iteration) {
+            const Change ch = stop_rule_change(d, h, e.reduce, s);
+            launch_solver_step(h, ch.gc, 1, ch.part, ch.npart);
             prof_mark(d, s, PK_REDUCE);
-          }
-          if (lazy) {
-            if (sw == max_sweeps - 2 || sw == max_sweeps - 1 || max_sweeps == 1)
-              k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision,
-                                                    0, nullptr, (sw == max_sweeps - 2) ? max_sweeps - 1 : 1, det_part(h), det_npart(h));
-          }
-          if (!st.fixed_iteration && look_at_state(h, sw, d->check_every, d->reduce_every)) {
+          } else if (e.count > 0) launch_solver_step(h, nullptr, e.count);
+          if (!st.fixed_iteration && look_at_state(h->last_sweeps, sw, d->check_every, d->reduce_every)) {
             dist_wait(d, s);
             read_scal(h);  // identical on every rank: same all-reduced sum (sweeps past the end are no-ops on the device)
             if (h->h_scal.p->done) break;
@@ -594,63 +592,32 @@ int polar_dist_step(polar_dist *d, polar_handle *h, int eflag, int vflag, polar_
         if (g > 0) HIPCHECK(hipStreamWaitEvent(s, d->ev_xdone[(g - 1) % kRing], 0));   // every halo dipole is its owner's final one
         prof_mark(d, s, PK_OTHER);
       } else if (!st.zodid) {
-        const bool lazy = st.fixed_iteration && gs;
         // `polar_accel m` with one exchange per sweep: the same mixing as above on the map "one sweep of every rank against the
         // halo dipoles of the previous one" (block-Jacobi across the ranks) -- everything on the compute stream, one all-reduce
         // (1 + 16 doubles) and one exchange of all halo rows per sweep
         const bool accel = gs && accel_begin(h, false);
-        double *ared = d->d_red.p + 64;   // [0] sum (dmu)^2, [1 .. 16] the dot products
         for (int sw = 0; sw < max_sweeps; sw++) {
           bool packed = false;
           sweep_once(h, false);
           prof_mark(d, s, PK_SWEEP);
-          if (accel) {
-            if (!lazy || sw < max_sweeps - 1) {
-              if (lazy) accel_export(h, ared + 1); else accel_export_fused(h, ared);   // (precision mode: the rank's change and its dot products leave one launch)
-              prof_mark(d, s, PK_ACCEL);
-              RCCLCHECK(R.AllReduce(ared, ared, 1 + 2 * POLAR_ACCEL_MAXM, ncclDouble, ncclSum, d->comm_red, s));
-              d->allreduces++;
-              prof_mark(d, s, PK_REDUCE);
-              if (lazy) accel_step(h, ared + 1); else accel_decide_mix(h, ared, false);   // (the decision on the all-reduced change and the coefficients: one launch)
-              prof_mark(d, s, PK_ACCEL);
-            }
-            if (lazy && (sw == max_sweeps - 2 || sw == max_sweeps - 1 || max_sweeps == 1))
-              k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision,
-                                                    0, nullptr, (sw == max_sweeps - 2) ? max_sweeps - 1 : 1, det_part(h), det_npart(h));
-          } else if (!st.fixed_iteration) {
-            // the stop rule (PS.cpp:1194-1210) needs the sum over all ranks: one all-reduced double every `reduce_every` sweeps;
-            // in between the end-of-sweep logic is told "not converged yet" (+inf)
-            const double *gc = d->d_red.p + 1;
-            if ((sw % d->reduce_every) == d->reduce_every - 1 || sw >= st.iterations_max) {
-              k_fold_change<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, d->d_red.p, det_part(h), det_npart(h));
-              RCCLCHECK(R.AllReduce(d->d_red.p, d->d_red.p, 1, ncclDouble, ncclSum, d->comm_red, s));
-              d->allreduces++;
-              gc = d->d_red.p;
-            }
+          const SweepEnd e = sweep_end(sw, max_sweeps, st.fixed_iteration != 0, gs, accel, d->reduce_every);
+          if (e.mix) accel_round(d, h, e.decide_in_mix, s);
+          if (e.count > 0 && !st.fixed_iteration) {
+            const Change ch = stop_rule_change(d, h, e.reduce, s);
             // Gauss-Seidel: the end-of-sweep logic and the pack of the halo dipoles in one launch (Jacobi flips its buffers in the
             // logic and packs afterwards)
             const long long ns = d->peers.empty() ? 0 : d->send_off[d->peers.size()];
             if (gs && ns > 0) {
               k_solver_step_gather<<<1 + nblk(ns, POLAR_NSLOT), POLAR_NSLOT, 0, s>>>(
-                  h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision, gc,
-                  gc == d->d_red.p ? nullptr : det_part(h), gc == d->d_red.p ? 0 : det_npart(h), ns, d->d_send_idx.p,
-                  h->sorted ? h->d_inv.p : nullptr, mu_view(h), d->d_send.p);
+                  h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision, ch.gc, ch.part, ch.npart, ns,
+                  d->d_send_idx.p, h->sorted ? h->d_inv.p : nullptr, mu_view(h), d->d_send.p);
               packed = true;
-            } else
-            k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision,
-                                                  gs ? 0 : 1, gc, 1, gc == d->d_red.p ? nullptr : det_part(h), gc == d->d_red.p ? 0 : det_npart(h));
-          } else if (lazy) {
-            if (sw == max_sweeps - 2 || sw == max_sweeps - 1 || max_sweeps == 1)
-              k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision,
-                                                    0, nullptr, (sw == max_sweeps - 2) ? max_sweeps - 1 : 1, det_part(h), det_npart(h));
-          } else {
-            k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision,
-                                                  gs ? 0 : 1, nullptr, 1, det_part(h), det_npart(h));
-          }
+            } else launch_solver_step(h, ch.gc, 1, ch.part, ch.npart);
+          } else if (e.count > 0) launch_solver_step(h, nullptr, e.count);
           if (!accel) prof_mark(d, s, PK_REDUCE);
           dist_exchange(d, h, packed);
           prof_mark(d, s, PK_XCHG);
-          if (!st.fixed_iteration && look_at_state(h, sw, d->check_every, d->reduce_every)) {
+          if (!st.fixed_iteration && look_at_state(h->last_sweeps, sw, d->check_every, d->reduce_every)) {
             dist_wait(d, s);
             read_scal(h);  // identical on every rank: same all-reduced sum (sweeps past the end are no-ops on the device)
             if (h->h_scal.p->done) break;

@@ -6,10 +6,14 @@
 //                    solve (PS.cpp:1113-1238), forces; the sweep launchers
 //   polar_color.hip  colour phases of the list-mode Gauss-Seidel (device colouring, re-validation)
 //   polar_dist.hip   multi-GPU driver over RCCL (polar_dist_*)
-// polar_plan.hpp (plain C++, tested on the host) holds the arithmetic that lays a step out: grid, pitches, k-vectors, nblk;
+// polar_plan.hpp (plain C++, tested on the host) holds the arithmetic that lays a step out: grid, pitches, k-vectors, nblk,
+// and the end of a sweep: what follows sweep sw of a solve (sweep_end: stop rule, mixing, all-reduce) and when the host looks
+// at the loop state (look_at_state) -- solve(), polar_step_sweep_end_n and both loops of polar_dist_step ask it, and
+// launch_solver_step (polar_step.hip) is the one launch of the stop rule;
 // polar_input.hpp (the same) what the entry points decide about their inputs: position scan, table analysis and packing, the
 // grid of polar_build_neighbors, the solver rule, the restart record.
-// polar_own.hpp holds the owners (DBuf, PinBuf, Event, Stream) with HipError and HIPCHECK.  Every device buffer, pinned buffer,
+// polar_own.hpp holds the owners (DBuf, PinBuf, Event, Stream) with HipError, NoDevice, HIPCHECK and error_code, the one
+// exception-to-POLAR_ERR_* ladder (guarded here, dist_guarded and the begin-agreement in polar_dist.hip).  Every device buffer, pinned buffer,
 // event and stream of the handle is a member of one of these types and frees itself: a new one is declared here and nowhere
 // else, polar_destroy is `delete h`, and ~polar_handle only waits for the streams before the members go.
 // No CPU implementation of the hot path anywhere: without a GPU every compute call fails.
@@ -49,9 +53,6 @@ using namespace polar;
 #define POLAR_MAX_CLASS_OFF 130   // phase classes of a colouring + 1: up to 64 colours, each split into boundary / interior rows on a sharded handle
 
 
-struct NoDevice : std::runtime_error {
-  NoDevice() : std::runtime_error("no usable HIP device: this library has no CPU fallback") {}
-};
 // one launch zeroing up to six small device buffers (sizes in bytes, multiples of 4)
 inline void zero_many(hipStream_t s, std::initializer_list<std::pair<void *, size_t>> bufs) {
   ZeroJobs jobs;
@@ -322,16 +323,8 @@ int guarded(polar_handle *h, F &&fn) {
   if (!h) return POLAR_ERR_STATE;
   try {
     return fn();
-  } catch (const InputError &e) {
-    return fail(h, POLAR_ERR_INPUT, e.what());
-  } catch (const Unsupported &e) {
-    return fail(h, POLAR_ERR_UNSUPPORTED, e.what());
-  } catch (const NoDevice &e) {
-    return fail(h, POLAR_ERR_NO_DEVICE, e.what());
-  } catch (const HipError &e) {
-    return fail(h, POLAR_ERR_HIP, e.what());
-  } catch (const std::exception &e) {
-    return fail(h, POLAR_ERR_STATE, e.what());
+  } catch (...) {
+    return error_code(h->err);
   }
 }
 
@@ -461,21 +454,6 @@ inline bool deterministic(const polar_handle *h) {
 // `deterministic yes` with the row sweep: where the end-of-sweep kernels find the sweep's partial sums of (dmu)^2
 inline const double *det_part(const polar_handle *h) { return (deterministic(h) && h->ph.st.dd_cutoff > 0.0 && h->sweep_kernel == 2 && h->lp_npart > 0) ? h->d_lp_part.p : nullptr; }
 inline int det_npart(const polar_handle *h) { return det_part(h) ? h->lp_npart : 0; }
-// When the host looks at the device-resident loop state (a stream synchronisation: the queue drains, ~12 us before the next
-// sweep starts).  Without history: after every `every`-th sweep.  With the sweep count of the handle's LAST solve -- counts
-// change by a sweep or two from step to step, in MD as in the resident bench -- the first look comes where that solve ended
-// (one look instead of eight at 31 sweeps, no launches past the end), then after every sweep for a few, then the old cadence.
-// Sweeps launched past the end of a finished solve are no-ops on the device either way.  `step` = sweeps per possible
-// change of the state (multi-GPU: the all-reduce cadence; the state can only flip after an all-reduced sweep).
-inline bool look_at_state(const polar_handle *h, int sw, int every, int step = 1) {
-  const int done_sweeps = sw + 1;
-  const int pred = h->last_sweeps;
-  if (pred <= 0) return (sw % every) == every - 1;
-  if (done_sweeps < pred) return (done_sweeps % 16) == 0;   // (a coarse look on the way: a solve that ends much earlier than the last one wastes at most 16 no-op sweeps)
-  const int past = done_sweeps - pred;
-  if (past <= 4 * step) return (past % step) == 0;
-  return (past % every) == 0;
-}
 inline bool tile_mode(const polar_handle *h) { return h->ph.st.dd_cutoff > 0.0 && h->sweep_kernel == 4; }
 // where the dipoles live during a solve (exchange and debug kernels): the sweep records in tile mode, else the AtomRecs
 inline MuView mu_view(const polar_handle *h) {
@@ -499,7 +477,11 @@ void prepare_lp(polar_handle *h);
 void sweep_once(polar_handle *h, bool ap);
 void sweep_phase(polar_handle *h, int color, int part);   // one colour phase of the list-mode Gauss-Seidel: part 0 = all its rows, 1 = boundary rows, 2 = interior rows
 void read_scal(polar_handle *h);
-void debug_trace(polar_handle *h, int sw, bool jacobi);
+void debug_trace(polar_handle *h, int sw);
+// the end-of-sweep logic for `count` sweeps (polar_plan.hpp, sweep_end); global_change: the all-reduced sum (dmu)^2 in device
+// memory (null: this handle's own); part / npart: where the sweep left partial sums to add in order
+void launch_solver_step(polar_handle *h, const double *global_change, int count, const double *part, int npart);
+inline void launch_solver_step(polar_handle *h, const double *global_change, int count) { launch_solver_step(h, global_change, count, det_part(h), det_npart(h)); }
 bool accel_begin(polar_handle *h, bool ap);
 void accel_export(polar_handle *h, double *dev_local_dots);
 void accel_step(polar_handle *h, const double *global_dots);

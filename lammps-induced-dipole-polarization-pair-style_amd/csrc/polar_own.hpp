@@ -1,8 +1,9 @@
 // polar_own.hpp -- the owners of what the library takes from the HIP runtime: device memory (DBuf), pinned host memory
 // (PinBuf), events and streams.  Each frees what it holds in its destructor, none can be copied, a moved-from one is empty: a
 // handle made of them (polar_handle, polar_dist) needs no list of what to free, and one whose creation failed half-way leaves
-// nothing behind.  Runtime API and standard library only -- no kernels, no handle --, so that a host compiler builds it
-// against a stand-in runtime (tests/own).
+// nothing behind.  With them the library's error types and the one place that turns an exception into a POLAR_ERR_* code
+// (error_code).  Runtime API, standard library and the host-only pair_host.hpp -- no kernels, no handle --, so that a host
+// compiler builds it against a stand-in runtime (tests/own).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -11,9 +12,25 @@
 #include <stdexcept>
 #include <string>
 
+#include "pair_host.hpp"
+
 struct HipError : std::runtime_error {
   explicit HipError(const std::string &m) : std::runtime_error(m) {}
 };
+struct NoDevice : std::runtime_error {
+  NoDevice() : std::runtime_error("no usable HIP device: this library has no CPU fallback") {}
+};
+// The exception in flight as the code an entry point returns, its text into `msg`: called inside a `catch (...)` (guarded,
+// dist_guarded, the begin-agreement of polar_dist_step).  Anything that is no std::exception travels on.
+inline int error_code(std::string &msg) {
+  try {
+    throw;
+  } catch (const polar::InputError &e) { msg = e.what(); return POLAR_ERR_INPUT;
+  } catch (const polar::Unsupported &e) { msg = e.what(); return POLAR_ERR_UNSUPPORTED;
+  } catch (const NoDevice &e) { msg = e.what(); return POLAR_ERR_NO_DEVICE;
+  } catch (const HipError &e) { msg = e.what(); return POLAR_ERR_HIP;
+  } catch (const std::exception &e) { msg = e.what(); return POLAR_ERR_STATE; }
+}
 #define HIPCHECK(expr)                                                                             \
   do {                                                                                             \
     hipError_t e_ = (expr);                                                                        \

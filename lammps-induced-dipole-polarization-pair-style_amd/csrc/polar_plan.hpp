@@ -1,8 +1,9 @@
 // polar_plan.hpp -- host-side step planning: the arithmetic that decides how a step is laid out (list grid, list pitches,
-// sweep stream, the Ewald k-vector table and its LDS tiling, block size of the dense Gauss-Seidel).
+// sweep stream, the Ewald k-vector table and its LDS tiling, block size of the dense Gauss-Seidel) and what follows a sweep of
+// the solve (stop rule, mixing, all-reduce, the host's looks at the loop state).
 //
-// Pure functions, plain C++17: no HIP header, no handle, nothing read from the environment.  polar_step.hip and polar_api.hip
-// call them between their launches; tests/test_plan_host.py drives the same functions on the host through
+// Pure functions, plain C++17: no HIP header, no handle, nothing read from the environment.  polar_step.hip, polar_api.hip and
+// polar_dist.hip call them between their launches; tests/test_plan_host.py drives the same functions on the host through
 // tests/plan/plan_host.cpp.  Functions that take the box are templates over anything with prd, xy, xz, yz, periodic and
 // triclinic (polar::Box, polar_common.hpp).
 #pragma once
@@ -163,5 +164,51 @@ inline SfacChunks ewald_sfac_chunks(int n, int nk, int tile) {
 inline bool dense_gs_fits(int n) { return n > 64 && 48.0 * (double)n * (double)n <= 3.2e10; }
 // atoms per block of the sweep (at least two blocks: dense_gs_fits needs n > 64)
 inline int dense_gs_block(int n) { return n >= 1024 ? 256 : n >= 384 ? 128 : 64; }
+
+// ---- the end of a sweep -------------------------------------------------------------------------------------------------
+// What follows sweep `sw` of at most max_sweeps = iterations_max + 1, the same for solve(), the stepwise calls and both
+// schedules of the multi-GPU driver (ranks that disagreed here would leave the loop at different sweeps, and one of them would
+// wait in an exchange for ever).  `accel`: Anderson mixing is on (what accel_begin returned); reduce_every: the driver's
+// all-reduce cadence, 0 on one handle.
+// Fixed-iteration Gauss-Seidel (`lazy`) takes no decision between sweeps: its end-of-sweep logic (k_solver_step) runs after
+// the last two sweeps only -- for all sweeps but the last at once, then for the last one, whose sum |dmu|^2 is the one
+// reported -- and it mixes after every sweep but the last.  Everything else decides after every sweep: in k_solver_step, or,
+// where it mixes, inside the mixing launch (k_solver_accel).  In precision mode the driver's stop rule reads the all-reduced
+// change every reduce_every-th sweep and on every sweep that can end the solve by running out of iterations ("not converged
+// yet" in between); with mixing the change rides the all-reduce of the dot products instead.
+struct SweepEnd {
+  bool mix;            // Anderson mixing follows this sweep ...
+  bool decide_in_mix;  // ... and carries the end-of-sweep decision (k_solver_step is not launched)
+  int count;           // sweeps the k_solver_step launched now accounts for; 0: none is launched
+  bool reduce;         // this sweep's change is all-reduced for the stop rule
+  bool jacobi;         // k_solver_step flips the dipole buffers
+};
+inline SweepEnd sweep_end(int sw, int max_sweeps, bool fixed_iteration, bool gs, bool accel, int reduce_every) {
+  const bool lazy = fixed_iteration && gs;
+  SweepEnd e;
+  e.mix = accel && (!lazy || sw < max_sweeps - 1);
+  e.decide_in_mix = accel && !lazy;
+  if (lazy) e.count = sw == max_sweeps - 2 ? max_sweeps - 1 : sw == max_sweeps - 1 ? 1 : 0;
+  else e.count = accel ? 0 : 1;
+  e.reduce = reduce_every > 0 && !fixed_iteration && !accel && ((sw % reduce_every) == reduce_every - 1 || sw >= max_sweeps - 1);
+  e.jacobi = !gs;
+  return e;
+}
+// When the host looks at the device-resident loop state (a stream synchronisation: the queue drains, ~12 us before the next
+// sweep starts).  Without history: after every `every`-th sweep.  With the sweep count of the handle's LAST converged solve
+// (`last_sweeps`; 0: none yet) -- counts change by a sweep or two from step to step, in MD as in the resident bench -- the
+// first look comes where that solve ended (one look instead of eight at 31 sweeps, no launches past the end), then after every
+// sweep for a few, then the old cadence.  Sweeps launched past the end of a finished solve are no-ops on the device either
+// way.  `step` = sweeps per possible change of the state (multi-GPU: the all-reduce cadence; the state can only flip after an
+// all-reduced sweep).
+inline bool look_at_state(int last_sweeps, int sw, int every, int step = 1) {
+  const int done_sweeps = sw + 1;
+  const int pred = last_sweeps;
+  if (pred <= 0) return (sw % every) == every - 1;
+  if (done_sweeps < pred) return (done_sweeps % 16) == 0;   // (a coarse look on the way: a solve that ends much earlier than the last one wastes at most 16 no-op sweeps)
+  const int past = done_sweeps - pred;
+  if (past <= 4 * step) return (past % step) == 0;
+  return (past % every) == 0;
+}
 
 }  // namespace polar

@@ -512,12 +512,12 @@ void read_scal(polar_handle *h) {
 void build_cluster_lists(polar_handle *) { throw std::logic_error("lab build only"); }
 #endif  // POLAR_LAB
 // `debug yes` (PS.cpp:1182-1191): u_polar after sweep `sw`, kept on the device until polar_get_debug_trace
-void debug_trace(polar_handle *h, int sw, bool /*jacobi*/) {
+void debug_trace(polar_handle *h, int sw) {
   if (!h->ph.st.debug) return;
   h->d_trace.ensure((size_t)h->ph.st.iterations_max + 8);
   if (sw > h->ph.st.iterations_max + 1) return;
   const MuView mv = mu_view(h);
-  k_debug_upolar<<<1, 1024, 0, h->stream>>>(h->nlocal, h->d_scal.p, mv.a, mv.b, mv.stride, h->d_ef_s.p, h->d_trace.p, sw, 0);  // Jacobi: like the reference, the value is formed BEFORE "mu = mu_new" (jacobi unused)
+  k_debug_upolar<<<1, 1024, 0, h->stream>>>(h->nlocal, h->d_scal.p, mv.a, mv.b, mv.stride, h->d_ef_s.p, h->d_trace.p, sw, 0);  // Jacobi: like the reference, the value is formed BEFORE "mu = mu_new"
   h->ntrace = sw + 1;
 }
 
@@ -590,9 +590,14 @@ static void launch_accel_mix(polar_handle *h, int tot, int nb) {
 // end of a sweep in solve(): where the host is due a look at the device-resident loop state (look_at_state; never in a
 // fixed-iteration run) it reads it; true = the stop rule has fired
 static bool sweep_stops(polar_handle *h, int sw, int check_every) {
-  if (h->ph.st.fixed_iteration || !look_at_state(h, sw, check_every)) return false;
+  if (h->ph.st.fixed_iteration || !look_at_state(h->last_sweeps, sw, check_every)) return false;
   read_scal(h);
   return h->h_scal.p->done != 0;
+}
+void launch_solver_step(polar_handle *h, const double *global_change, int count, const double *part, int npart) {
+  const polar_settings &st = h->ph.st;
+  k_solver_step<<<1, POLAR_NSLOT, 0, h->stream>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision,
+                                                  (st.polar_gs || st.polar_gs_ranked) ? 0 : 1, global_change, count, part, npart);
 }
 
 void solve(polar_handle *h, bool ap, polar_result *out) {
@@ -616,18 +621,14 @@ void solve(polar_handle *h, bool ap, polar_result *out) {
 #ifdef POLAR_LAB
     if (!ap && h->sweep_kernel == 2 && h->lp_pairs && !deterministic(h)) build_units(h);
 #endif
-    // fixed-iteration GS takes no decision between sweeps: its end-of-sweep logic is applied in two
-    // launches (all sweeps but the last, then the last one, whose sum |dmu|^2 is the one reported)
-    const bool lazy = st.fixed_iteration && gs;
     const bool accel = accel_begin(h, ap);   // `polar_accel m`: Anderson mixing between the sweeps
     for (int sw = 0; sw < max_sweeps; sw++) {
       sweep_once(h, ap);
-      debug_trace(h, sw, !gs);
-      if (accel && lazy && sw < max_sweeps - 1) accel_step(h, nullptr);   // (no decision to wait for; nothing after the last sweep)
-      if (lazy && sw < max_sweeps - 2) continue;
-      const int count = (lazy && sw == max_sweeps - 2) ? max_sweeps - 1 : 1;
-      if (accel && !lazy) accel_decide_mix(h, nullptr, true);   // differences, [decision + coefficients], mix: the mix is a no-op once the stop rule has fired (the result is G(x_k) of the last sweep)
-      else k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision, gs ? 0 : 1, nullptr, count, det_part(h), det_npart(h));
+      debug_trace(h, sw);
+      const SweepEnd e = sweep_end(sw, max_sweeps, st.fixed_iteration != 0, gs, accel, 0);
+      if (e.mix && e.decide_in_mix) accel_decide_mix(h, nullptr, true);   // differences, [decision + coefficients], mix: the mix is a no-op once the stop rule has fired (the result is G(x_k) of the last sweep)
+      else if (e.mix) accel_step(h, nullptr);   // (fixed-iteration GS: no decision to wait for; nothing after the last sweep)
+      if (e.count > 0) launch_solver_step(h, nullptr, e.count);
       if (sweep_stops(h, sw, check_every)) break;
     }
   } else if (h->dense_gs) {  // exact-order blocked Gauss-Seidel on the HBM-resident tensor
@@ -677,8 +678,8 @@ void solve(polar_handle *h, bool ap, polar_result *out) {
 #undef POLAR_GS_BLK
         prev = b0; flip ^= 1;
       }
-      debug_trace(h, sw, false);
-      if (!tail_on) k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision, 0, nullptr, 1, h->d_gs_part.p, npart);
+      debug_trace(h, sw);
+      if (!tail_on) launch_solver_step(h, nullptr, 1, h->d_gs_part.p, npart);
       if (sweep_stops(h, sw, check_every)) break;
     }
   } else {  // exact-order blocked Gauss-Seidel, matrix-free (systems whose tensor does not fit)
@@ -706,8 +707,8 @@ void solve(polar_handle *h, bool ap, polar_result *out) {
           k_gs_block_push<1><<<nblk(n, POLAR_ROWS_PER_BLOCK), POLAR_BLOCK, 0, s>>>(n, b0, h->d_order.p, h->d_pos.p, h->d_rec0.p, h->box, st.polar_damp, h->d_dmu.p, h->d_F.p, h->d_scal.p);
         }
       }
-      debug_trace(h, sw, false);
-      k_solver_step<<<1, POLAR_NSLOT, 0, s>>>(h->d_scal.p, h->d_slots.p, norm_count(h), st.fixed_iteration, st.iterations_max, st.polar_precision, 0, nullptr, 1, nullptr, 0);
+      debug_trace(h, sw);
+      launch_solver_step(h, nullptr, 1, nullptr, 0);
       if (sweep_stops(h, sw, check_every)) break;
     }
   }

@@ -15,6 +15,8 @@
 //   borrow         live streams while a Stream lends a stream made elsewhere | after the Stream has gone | after its maker
 //                  destroyed it; then the same through release()
 //   poison         first and last byte of a fresh DBuf<unsigned char> of 100 (0x7F with POLAR_POISON=1 in the environment)
+//   errors         one exception of each class the entry points tell apart (InputError, Unsupported, NoDevice, HipError, any other
+//                  std::exception), each on a line: the code error_code gives it, then its message
 //   live           live
 #include <cstdio>
 #include <cstring>
@@ -158,6 +160,19 @@ int main() {
       DBuf<unsigned char> b;
       b.ensure(100);
       printf("%d %d\n", (int)b.p[0], (int)b.p[b.cap - 1]);
+    } else if (!strcmp(cmd, "errors")) {
+      for (int k = 0; k < 5; k++) {
+        std::string msg = "stale";
+        int code = 0;
+        try {
+          if (k == 0) throw polar::InputError("bad input");
+          if (k == 1) throw polar::Unsupported("not offered");
+          if (k == 2) throw NoDevice();
+          if (k == 3) throw HipError("hipFoo failed");
+          throw std::logic_error("out of order");
+        } catch (...) { code = error_code(msg); }
+        printf("%d %s\n", code, msg.c_str());
+      }
     } else if (!strcmp(cmd, "live")) {
       print_live();
     } else {

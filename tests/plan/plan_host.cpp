@@ -13,6 +13,8 @@
 //   tile    nm                                   -> lds_per_atom tile
 //   chunks  n nk tile                            -> kb nchunk chunk
 //   gs      n                                    -> fits B
+//   sweepend sw max_sweeps fixed gs accel reduce_every -> mix decide_in_mix count reduce jacobi
+//   look    last_sweeps sw every step            -> 0 | 1
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -101,6 +103,15 @@ int main() {
       int n;
       if (!rd(n)) return 2;
       printf("%d %d\n", polar::dense_gs_fits(n) ? 1 : 0, polar::dense_gs_block(n));
+    } else if (!strcmp(cmd, "sweepend")) {
+      int sw, max_sweeps, fixed, gs, accel, reduce_every;
+      if (!rd(sw) || !rd(max_sweeps) || !rd(fixed) || !rd(gs) || !rd(accel) || !rd(reduce_every)) return 2;
+      const polar::SweepEnd e = polar::sweep_end(sw, max_sweeps, fixed != 0, gs != 0, accel != 0, reduce_every);
+      printf("%d %d %d %d %d\n", e.mix ? 1 : 0, e.decide_in_mix ? 1 : 0, e.count, e.reduce ? 1 : 0, e.jacobi ? 1 : 0);
+    } else if (!strcmp(cmd, "look")) {
+      int last_sweeps, sw, every, step;
+      if (!rd(last_sweeps) || !rd(sw) || !rd(every) || !rd(step)) return 2;
+      printf("%d\n", polar::look_at_state(last_sweeps, sw, every, step) ? 1 : 0);
     } else {
       fprintf(stderr, "unknown command %s\n", cmd);
       return 2;

@@ -96,6 +96,19 @@ def test_poison_fills_a_new_block(own):
     assert own(("poison",), env={"POLAR_POISON": "1"})[0] == ["127", "127"]
 
 
+def test_error_code_tells_the_five_classes_apart(own):
+    """error_code (the one catch ladder of guarded, dist_guarded and the begin-agreement of polar_dist_step): the code of
+    include/polar_mi355x.h for each class, and the exception's own text."""
+    t = own(("errors",))
+    assert [(int(ln[0]), " ".join(ln[1:])) for ln in t] == [
+        (-1, "bad input"),                                                   # InputError    POLAR_ERR_INPUT
+        (-4, "not offered"),                                                 # Unsupported   POLAR_ERR_UNSUPPORTED
+        (-2, "no usable HIP device: this library has no CPU fallback"),      # NoDevice      POLAR_ERR_NO_DEVICE
+        (-3, "hipFoo failed"),                                               # HipError      POLAR_ERR_HIP
+        (-5, "out of order"),                                                # the rest      POLAR_ERR_STATE
+    ]
+
+
 def test_program_ends_with_nothing_live(own):
     """All commands in one run: the exit status (0 only with every count at zero) and the leak check at exit."""
     out = own(("caps", 3, 5, 70, 9), ("scope",), ("release",), ("vector", 70), ("moves",), ("fail",), ("borrow",), ("live",))

@@ -1,5 +1,6 @@
 """Host-side step planning (csrc/polar_plan.hpp: cell widths, list grid, list pitches, occupied volume, sweep stream, the
-Ewald k-vector table with its LDS tiling and chunking, block size of the dense Gauss-Seidel) on the host.
+Ewald k-vector table with its LDS tiling and chunking, block size of the dense Gauss-Seidel, and the end-of-sweep schedule of
+the solve: sweep_end and look_at_state) on the host.
 
 The header is plain C++: g++ builds tests/plan/plan_host.cpp around it, a stand-alone program (with the address and
 undefined-behaviour sanitizers where the toolchain has them) that reads commands on stdin and prints what the functions
@@ -262,3 +263,165 @@ def test_dense_gauss_seidel_block_size_and_fit(plan):
     assert [got[n][1] for n in (65, 383, 384, 1023, 1024, 25819)] == [64, 64, 128, 128, 256, 256]
     assert got[64][0] == 0 and got[65][0] == 1
     assert got[25819][0] == 1 and got[25820][0] == 0
+
+
+# ---- the end of a sweep -------------------------------------------------------------------------------------------------
+# The four places that wrote the rule out by hand before polar_plan.hpp held it, transcribed from commit
+# 0482dd533848ea305e430bb1eb1e2632b5869e31: per sweep (mixing runs, the decision rides the mix, count of k_solver_step or 0,
+# the change is all-reduced).
+def _parent_solve_list_loop(max_sweeps, fixed, gs, accel, reduce_every=0):
+    """polar_step.hip, solve(), the list / Jacobi loop of commit 0482dd5 (one handle: nothing is all-reduced)."""
+    lazy = fixed and gs
+    out = []
+    for sw in range(max_sweeps):
+        mix, decide, count = False, False, 0
+        if accel and lazy and sw < max_sweeps - 1:
+            mix = True                                        # accel_step(h, nullptr)
+        if lazy and sw < max_sweeps - 2:
+            out.append((mix, decide, count, False))
+            continue
+        c = max_sweeps - 1 if (lazy and sw == max_sweeps - 2) else 1
+        if accel and not lazy:
+            mix, decide = True, True                          # accel_decide_mix(h, nullptr, true)
+        else:
+            count = c                                         # k_solver_step(..., count, ...)
+        out.append((mix, decide, count, False))
+    return out
+
+
+def _parent_dist_phased_loop(max_sweeps, fixed, gs, accel, reduce_every):
+    """polar_dist.hip, polar_dist_step, the per-phase schedule of commit 0482dd5 (`if (!st.zodid && phased)`; phased needs gs)."""
+    assert gs
+    iterations_max = max_sweeps - 1
+    lazy = fixed != 0
+    out = []
+    for sw in range(max_sweeps):
+        mix, decide, count, reduce = False, False, 0, False
+        if accel and (not lazy or sw < max_sweeps - 1):
+            mix = True                                        # export, all-reduce of 1 + 16 doubles, ...
+            decide = not lazy                                 # ... accel_step (lazy) or accel_decide_mix
+        elif not fixed:
+            if (sw % reduce_every) == reduce_every - 1 or sw >= iterations_max:
+                reduce = True                                 # k_fold_change, all-reduce of one double
+            count = 1
+        if lazy:
+            if sw == max_sweeps - 2 or sw == max_sweeps - 1 or max_sweeps == 1:
+                count = max_sweeps - 1 if sw == max_sweeps - 2 else 1
+        out.append((mix, decide, count, reduce))
+    return out
+
+
+def _parent_dist_sweep_loop(max_sweeps, fixed, gs, accel, reduce_every):
+    """polar_dist.hip, polar_dist_step, the one-exchange-per-sweep schedule of commit 0482dd5 (`else if (!st.zodid)`)."""
+    iterations_max = max_sweeps - 1
+    lazy = fixed and gs
+    accel = gs and accel
+    out = []
+    for sw in range(max_sweeps):
+        mix, decide, count, reduce = False, False, 0, False
+        if accel:
+            if not lazy or sw < max_sweeps - 1:
+                mix = True
+                decide = not lazy
+            if lazy and (sw == max_sweeps - 2 or sw == max_sweeps - 1 or max_sweeps == 1):
+                count = max_sweeps - 1 if sw == max_sweeps - 2 else 1
+        elif not fixed:
+            if (sw % reduce_every) == reduce_every - 1 or sw >= iterations_max:
+                reduce = True
+            count = 1                                         # k_solver_step_gather or k_solver_step
+        elif lazy:
+            if sw == max_sweeps - 2 or sw == max_sweeps - 1 or max_sweeps == 1:
+                count = max_sweeps - 1 if sw == max_sweeps - 2 else 1
+        else:
+            count = 1
+        out.append((mix, decide, count, reduce))
+    return out
+
+
+def _parent_sweep_end_n_accepts(count, fixed, gs):
+    """polar_api.hip, polar_step_sweep_end_n of commit 0482dd5: count >= 1, and count > 1 only with fixed-iteration GS."""
+    if count < 1:
+        return False
+    if count > 1 and not (gs and fixed):
+        return False
+    return True
+
+
+def _sweep_end_cases(reduce_everys, gs_values=(0, 1)):
+    return [(m, f, g, a, r) for m in range(1, 7) for f in (0, 1) for g in gs_values for a in ((0, 1) if g else (0,))
+            for r in reduce_everys]
+
+
+def _sweep_end(plan, cases):
+    """{case: [(mix, decide_in_mix, count, reduce, jacobi) per sweep]} from one run of the program."""
+    cmds = [("sweepend", sw, m, f, g, a, r) for (m, f, g, a, r) in cases for sw in range(m)]
+    rows = iter(plan(*cmds))
+    return {c: [tuple(int(v) for v in next(rows)) for _ in range(c[0])] for c in cases}
+
+
+@pytest.mark.parametrize("parent,reduce_everys,gs_values", [
+    (_parent_solve_list_loop, (0,), (0, 1)),
+    (_parent_dist_phased_loop, (1, 2, 3), (1,)),       # (that loop runs Gauss-Seidel only: `shared` asks for gs)
+    (_parent_dist_sweep_loop, (1, 2, 3), (0, 1)),
+], ids=["solve", "dist_phased", "dist_sweep"])
+def test_sweep_end_is_the_rule_the_loops_wrote_out(plan, parent, reduce_everys, gs_values):
+    cases = _sweep_end_cases(reduce_everys, gs_values)
+    got = _sweep_end(plan, cases)
+    for c in cases:
+        m, f, g, a, r = c
+        want = [tuple(int(v) for v in t) for t in parent(m, f, g, a, r)]
+        assert [t[:4] for t in got[c]] == want, c
+        assert all(t[4] == (0 if g else 1) for t in got[c]), c          # every launch site passed `gs ? 0 : 1`
+
+
+def test_sweep_end_counts_are_those_the_stepwise_call_accepts(plan):
+    cases = _sweep_end_cases((0, 1, 2, 3))
+    for (m, f, g, a, r), rows in _sweep_end(plan, cases).items():
+        for t in rows:
+            if t[2] != 0:
+                assert _parent_sweep_end_n_accepts(t[2], f, g), (m, f, g, a, r, t)
+            if t[2] > 1:
+                assert f and g
+
+
+def test_sweep_end_properties(plan):
+    cases = _sweep_end_cases((0, 1, 2, 3))
+    for (m, f, g, a, r), rows in _sweep_end(plan, cases).items():
+        key = (m, f, g, a, r)
+        counts = [t[2] for t in rows]
+        if f and g:                                                      # lazy: fixed-iteration Gauss-Seidel
+            assert sum(counts) == m, key                                 # every sweep is accounted for once
+            assert counts[-1] == 1, key                                  # the last launch follows the last sweep, alone
+            assert all(c == 0 for c in counts[:-2]), key
+            if a:
+                assert [t[0] for t in rows] == [1] * (m - 1) + [0], key  # mixing after every sweep but the last
+                assert all(t[1] == 0 for t in rows), key
+        if not f:                                                        # precision mode: one decision per sweep
+            assert all((t[2] == 1) != (t[1] == 1) for t in rows), key
+            assert all(t[0] == t[1] for t in rows), key                  # and a decision in the mix means there is a mix
+            if r > 0 and not a:
+                assert rows[m - 1][3] == 1, key                          # sw >= iterations_max reduces
+                assert [t[3] for t in rows[:m - 1]] == [1 if sw % r == r - 1 else 0 for sw in range(m - 1)], key
+        if r == 0 or f or a:
+            assert all(t[3] == 0 for t in rows), key
+
+
+def _parent_look_at_state(last_sweeps, sw, every, step=1):
+    """polar_handle.hpp, look_at_state of commit 0482dd5, with h->last_sweeps as an argument."""
+    done_sweeps = sw + 1
+    pred = last_sweeps
+    if pred <= 0:
+        return (sw % every) == every - 1
+    if done_sweeps < pred:
+        return (done_sweeps % 16) == 0
+    past = done_sweeps - pred
+    if past <= 4 * step:
+        return (past % step) == 0
+    return (past % every) == 0
+
+
+def test_look_at_state_is_the_parents(plan):
+    cases = [(last, sw, every, step) for last in range(41) for sw in range(81) for every in (1, 4) for step in (1, 2, 3)]
+    got = [int(v[0]) for v in plan(*[("look", *c) for c in cases])]
+    assert got == [int(_parent_look_at_state(*c)) for c in cases]
+    assert 0 in got and 1 in got
