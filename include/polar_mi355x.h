@@ -151,7 +151,15 @@ double polar_pair_single(const polar_handle *h, double qi, double qj, int itype,
  * the length of the list).  Both are 0 before the first compute call.  Unlike the other names these two are NOT a plain
  * lookup: the call waits for the handle's streams, may launch a small summing kernel and copies the result from the device,
  * and it updates the handle's copy of the two numbers (the pointer returned stays valid until the next such call).  Not
- * for use inside a step loop; NULL when the device reports an error (message in polar_last_error). */
+ * for use inside a step loop; NULL when the device reports an error (message in polar_last_error).
+ * Two more of the same kind (dim 0, doubles, summed on the device when asked for, 0 before the first compute call):
+ * "nl_entries", the entries the last build of the library's own full list wrote (every partner within max(cut_coul,
+ * dd_cutoff) that has a charge or a polarizability: a site with q == 0 and alpha == 0 adds exactly nothing to the static
+ * field or the polarization forces and is left out; 0 in exact mode, which has no list), and "force_rows", the rows the last
+ * polarization-force launch had to walk (every row whose atom is not such a site; worked out from the atoms' records by the
+ * kernel's own test when asked for, not counted inside the launch).  Both read 0 again after polar_set_atoms or
+ * polar_set_row_range, until the next compute call.  A handle created with POLAR_NL_INERT=0 in the
+ * environment lists every partner and walks every row. */
 const void *polar_pair_extract(const polar_handle *h, const char *name, int *dim);
 int polar_get_settings(const polar_handle *h, polar_settings *out);
 

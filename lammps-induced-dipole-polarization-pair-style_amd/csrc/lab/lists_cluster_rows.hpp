@@ -112,7 +112,7 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_cl_build(ClusterRows cl,
         int hits = 0;
         if (j < b && j != m0 && j != m1 && j != m2 && j != m3) {
           const double4 rj = pos4[j];
-          if (__double2loint(rj.w)) {  // polarizable
+          if (__double2loint(rj.w) >= SITE_POLAR) {  // polarizable
 #pragma unroll
             for (int k = 0; k < 4; k++) {
               double ex, ey, ez;

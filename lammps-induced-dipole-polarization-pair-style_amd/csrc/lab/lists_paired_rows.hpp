@@ -104,7 +104,7 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_dd_units(int nunits, con
         bool inA = false, inB = false;
         if (j < b) {
           const double4 rj = pos4[j];
-          if (__double2loint(rj.w)) {   // polarizable
+          if (__double2loint(rj.w) >= SITE_POLAR) {   // polarizable
             double ex, ey, ez;
             const bool shA = min_image_rint_w<TRI>(box, rA.x, rA.y, rA.z, rj.x, rj.y, rj.z, ex, ey, ez);
             inA = j != iA && ex * ex + ey * ey + ez * ez < ddcutsq;

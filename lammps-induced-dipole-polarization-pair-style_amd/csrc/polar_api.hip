@@ -64,6 +64,28 @@ void lj_counters(polar_handle *h) {
   }
   h->lj_entries = (double)total; h->lj_walked = (double)walked;
 }
+// polar_pair_extract "nl_entries" / "force_rows": the same way -- the entries the last list build wrote into the full list
+// (0 in exact mode: there is no list) and the rows the last force launch did not skip, summed on the device when asked.
+// "force_rows" is NOT observed in the launch (no per-row atomic in the hot kernel): k_nl_inert_sums applies the kernel's own
+// test, site_is_inert(q, alpha), to the records and rows that launch read.  Both are 0 after polar_set_atoms or
+// polar_set_row_range until the next compute call: nl_cnt, the rows and the records on the device belong to the last step.
+void inert_counters(polar_handle *h) {
+  h->nl_entries = h->force_rows = 0.0;
+  if (!h->have_device || !h->force_ran || h->force_nrows <= 0) return;   // (no step yet)
+  HIPCHECK(hipSetDevice(h->device));
+  if (!h->nl_inert) h->force_rows = (double)h->force_nrows;   // nothing is skipped
+  if (!h->force_listed && !h->nl_inert) return;
+  h->d_inert_sums.ensure(2);
+  unsigned long long sums[2] = {0ull, 0ull};
+  HIPCHECK(hipMemsetAsync(h->d_inert_sums.p, 0, 2 * sizeof(unsigned long long), h->stream));
+  const int n = h->force_listed ? h->nlocal : 0, m = std::max(n, h->force_nrows);
+  k_nl_inert_sums<<<nblk(m, 1024), 256, 0, h->stream>>>(n, h->force_listed ? h->d_nl_cnt.p : nullptr, h->nl_pitch, h->nl_inert ? h->force_nrows : 0,
+                                                      own_rows(h), h->d_rec0.p, h->d_inert_sums.p);   // (rows and records of the last step)
+  HIPCHECK(hipMemcpyAsync(sums, h->d_inert_sums.p, sizeof(sums), hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  h->nl_entries = (double)sums[0];
+  if (h->nl_inert) h->force_rows = (double)sums[1];
+}
 // The half list of a reneighbor step on its way to the device (PS.cpp:232-247 reads list->firstneigh): rows are packed in
 // ilist order into two pinned 32 MB buffers by the helper threads -- each thread checking its entries on the way -- and a
 // buffer travels (hipMemcpyAsync from pinned memory: the full PCIe rate) while the next one is packed.  270 MB at 135k atoms:
@@ -205,6 +227,7 @@ int polar_create(int device, polar_handle **out) {
     if (getenv("POLAR_NO_OVERLAP")) h->overlap_lj = false;
     if (const char *e = getenv("POLAR_LJ_PERS")) h->lj_pers = atoi(e);
     if (const char *e = getenv("POLAR_LJ_SKIN")) h->lj_skin = atoi(e) != 0;   // 0: the LJ/Coulomb rows are walked whole (the A/B partner of the distance classes)
+    if (const char *e = getenv("POLAR_NL_INERT")) h->nl_inert = atoi(e) != 0;   // 0: inert sites stay in the full list and keep their force rows (the A/B partner)
     if (const char *e = getenv("POLAR_LJ_PERS_THREADS")) h->lj_pers_threads = std::max(256, std::min(POLAR_LJ_PERS_THREADS, (atoi(e) / 64) * 64));
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess) h->ncu = ncu; }
     h->h_scal.ensure(1);
@@ -284,6 +307,13 @@ const void *polar_pair_extract(const polar_handle *h, const char *name, int *dim
     polar_handle *m = const_cast<polar_handle *>(h);
     if (guarded(m, [&]() { lj_counters(m); return POLAR_OK; }) != POLAR_OK) return nullptr;
     return name[3] == 'w' ? &h->lj_walked : &h->lj_entries;
+  }
+  // entries the last list build wrote into the full list / rows the last force launch walked (fewer than all partners and
+  // all rows where the system holds inert sites: no charge, no polarizability)
+  if (strcmp(name, "nl_entries") == 0 || strcmp(name, "force_rows") == 0) {
+    polar_handle *m = const_cast<polar_handle *>(h);
+    if (guarded(m, [&]() { inert_counters(m); return POLAR_OK; }) != POLAR_OK) return nullptr;
+    return name[0] == 'n' ? &h->nl_entries : &h->force_rows;
   }
   if (dim) *dim = 2;
   if (strcmp(name, "epsilon") == 0) return h->ph.epsilon.data();
@@ -382,6 +412,7 @@ int polar_set_atoms(polar_handle *h, int nlocal, int nghost, const double *x, co
     need_device(h);
     HIPCHECK(hipSetDevice(h->device));
     if (nlocal < 0 || nghost < 0) throw InputError("negative atom count");
+    h->force_ran = false;   // "nl_entries" / "force_rows" describe a compute call on THESE atoms: 0 until the next one (inert_counters)
     const size_t nall = (size_t)nlocal + nghost;
     // the checks and the copies into the pinned staging area by the helper threads (a reneighbor step of an MD run hands all
     // five arrays over: single-threaded checks + five copies out of pageable memory cost 1.3 ms at 258k atoms)
@@ -701,6 +732,7 @@ int polar_set_row_range(polar_handle *h, int lo, int hi) {
   return guarded(h, [&]() {
     if (lo < 0 || (hi >= 0 && hi < lo)) throw InputError("bad row range");
     h->row_lo = lo; h->row_hi = hi;
+    h->force_ran = false;   // (the rows of the last force launch are not the handle's rows any more: inert_counters)
     return POLAR_OK;
   });
 }

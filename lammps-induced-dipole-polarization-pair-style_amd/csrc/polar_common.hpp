@@ -301,6 +301,15 @@ __host__ __device__ __forceinline__ unsigned lp_slot32(unsigned e, int qm) {
 #define POLAR_NL_SAMEMOL 0x40000000
 #define POLAR_NL_MASK 0x3FFFFFFF
 
+// The kind of a site, the low word of pos4[i].w (k_pack writes it every step from the resident q and alpha):
+//   SITE_INERT    q == 0 and alpha == 0 (an LJ-only site): no entry in any row of the full list -- as a partner it adds an
+//                 exact zero to the static field, the polarization force and the rank metric
+//   SITE_CHARGED  alpha == 0 but q != 0: in the full list, not in the dipole lists
+//   SITE_POLAR    alpha != 0 (whatever q is): everywhere
+// "polarizable" is `>= SITE_POLAR`, "listed" is `!= SITE_INERT`: one compare each.
+enum { SITE_INERT = 0, SITE_CHARGED = 1, SITE_POLAR = 2 };
+__host__ __device__ __forceinline__ bool site_is_inert(double q, double alpha) { return q == 0.0 && alpha == 0.0; }
+
 // Wave-cooperative gather of 64 atom records for the lane-per-pair row kernels (list mode).  A
 // scattered load costs the vector-memory address unit one 64-byte line per LANE; here lane k of quad
 // q loads piece k of the records of lanes q, 16+q, 32+q, 48+q (4 instructions, one line per quad

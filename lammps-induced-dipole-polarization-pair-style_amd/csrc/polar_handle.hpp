@@ -135,6 +135,11 @@ struct polar_handle {
   bool lj_ran = false;      // an LJ/Coulomb kernel has run on the list in force
   bool lj_sym_last = false, lj_walk_last = false; int lj_rows_last = 0;   // the last a3 launch: symmetrised rows, walked by class, rows
   double lj_walked = 0.0, lj_entries = 0.0;   // polar_pair_extract "lj_walked" / "lj_entries"
+  // inert sites (q == 0 and alpha == 0, SITE_INERT in polar_common.hpp) are left out of the full list and their force rows are skipped
+  int nl_inert = 1;         // POLAR_NL_INERT=0: every partner listed, every force row walked
+  bool force_ran = false, force_listed = false; int force_nrows = 0;   // the last force launch: list mode, its rows
+  double nl_entries = 0.0, force_rows = 0.0;   // polar_pair_extract "nl_entries" / "force_rows"
+  DBuf<unsigned long long> d_inert_sums;
   DBuf<AtomRec> d_rec0, d_rec1;
   DBuf<Scal> d_scal;
   DBuf<double> d_slots;

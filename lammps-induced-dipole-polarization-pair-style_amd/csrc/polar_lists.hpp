@@ -216,7 +216,7 @@ static __global__ void k_color_adj(int n, const double4 *__restrict__ pos4, cons
   if (i >= n) return;
   const double4 ri = pos4[i];
   const int o = perm[i];
-  const bool row = __double2loint(ri.w) && o >= own_lo && o < own_hi;
+  const bool row = __double2loint(ri.w) >= SITE_POLAR && o >= own_lo && o < own_hi;
   color_s[i] = -1;
   if (!row) { deg[i] = -1; prio[i] = 0ull; return; }
   int cc[3];
@@ -565,7 +565,7 @@ struct NlRunLanes {
 };
 // One wave per atom row; the lanes walk the atoms of the row's stencil of cells (contiguous s ranges) 64 at a time;
 // ballot + popcount compacts in order.  Single pass into the pitched lists:
-//   nl : every j with rsq <= cutallsq                      (static field, forces, rank metric)
+//   nl : every j with rsq <= cutallsq that is not inert   (static field, forces, rank metric; SITE_INERT, polar_common.hpp)
 //   dd : alpha_i != 0, alpha_j != 0 and rsq < ddcutsq      (the dipole sweep stream)
 // cnt[] receives the TRUE counts; writes stop at the pitch and *overflow is raised.
 // DENSE (the product path): the runs of a row atom's stencil are laid end to end and walked in trips of 64 candidates
@@ -574,7 +574,8 @@ struct NlRunLanes {
 // out entry for entry the same (tests/test_gpu_nl_dense_trips.py).
 // gfx950 -O3, dense: trip loop of <false, false> 66 vector instructions (20 FP64) + 64 scalar + 5 memory, 6 of the 66 in
 // the run-table walk (per-run form before: 72 / 20 + 45 + 5; tests/test_nl_isa_budget.py); <false, true> 72 / 21,
-// <true, false> 69 / 23, <true, true> 75 / 24.  VGPRs <false,false> 26, <false,true> 27, <true,false> 22, <true,true> 23
+// <true, false> 69 / 23, <true, true> 75 / 24 (counted before inert candidates were left out of nl, which adds a compare:
+// <false, false> is 67 / 20 + 67 scalar now).  VGPRs <false,false> 26, <false,true> 27, <true,false> 22, <true,true> 23
 // (before: 48 / 54 / 44 / 53 -- the row atom is wave-uniform now and lives in scalar registers; cap 64:
 // tests/test_kernel_resources.py).
 template <bool TRI, bool RECHECK, bool DENSE = true>
@@ -596,8 +597,8 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_nl_build(const int *__re
   const int row = blockIdx.x * POLAR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (row >= nrows) return;
   const int i = __builtin_amdgcn_readfirstlane(rows ? rows[row] : row);  // s space: the atoms of cell c are the indices [cell_first[c], cell_first[c+1])
-  const double4 ri = pos4[i];            // {x, y, z, (molecule, polarizable)}
-  const int imol = __double2hiint(ri.w), ipol = __double2loint(ri.w);
+  const double4 ri = pos4[i];            // {x, y, z, (molecule, kind of site)}
+  const int imol = __double2hiint(ri.w), ipol = __double2loint(ri.w) >= SITE_POLAR;
   // colour re-validation on reneighbor steps (color_s != NULL): the colouring of the previous list stays in use unless
   // two polarizable atoms of one colour have come closer than the colour distance
   const int icol = (RECHECK && color_s && ipol) ? color_s[i] : -2;
@@ -700,12 +701,15 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_nl_build(const int *__re
     // lane masks straight from the compares, combined as scalars (a ballot of a combined predicate goes through a select
     // and a second compare per list)
     const unsigned long long m_pair = __builtin_amdgcn_ballot_w64(j != i);
-    const unsigned long long m_nl = m_pair & __builtin_amdgcn_ballot_w64(rsq <= cutallsq);
-    const unsigned long long m_dd = m_pair & dd_im & __builtin_amdgcn_ballot_w64(__double2loint(rj.w) != 0) & __builtin_amdgcn_ballot_w64(rsq < ddcutsq);
+    // an inert candidate (SITE_INERT: no charge, no polarizability) gets no nl entry: every reader of nl would add an exact
+    // zero for it (polar_common.hpp)
+    const int jkind = __double2loint(rj.w);
+    const unsigned long long m_nl = m_pair & __builtin_amdgcn_ballot_w64(rsq <= cutallsq) & __builtin_amdgcn_ballot_w64(jkind != SITE_INERT);
+    const unsigned long long m_dd = m_pair & dd_im & __builtin_amdgcn_ballot_w64(jkind >= SITE_POLAR) & __builtin_amdgcn_ballot_w64(rsq < ddcutsq);
     wrap_m |= m_dd & shifted;
-    const bool in_nl = (j != i) & (rsq <= cutallsq);  // (the lane's own bit of m_nl / m_dd: the same compares)
-    const bool in_dd = (j != i) & (dd_im != 0ull) & (__double2loint(rj.w) != 0) & (rsq < ddcutsq);
-    if (RECHECK) { if (icol >= 0 && j != i && rsq < colordistsq && __double2loint(rj.w) != 0 && color_s[j] == icol) clash = true; }
+    const bool in_nl = (j != i) & (rsq <= cutallsq) & (jkind != SITE_INERT);  // (the lane's own bit of m_nl / m_dd: the same compares)
+    const bool in_dd = (j != i) & (dd_im != 0ull) & (jkind >= SITE_POLAR) & (rsq < ddcutsq);
+    if (RECHECK) { if (icol >= 0 && j != i && rsq < colordistsq && jkind >= SITE_POLAR && color_s[j] == icol) clash = true; }
     int jmol = __double2hiint(rj.w);
     asm("" : "+v"(jmol));  // (keeps the compare on the 32-bit word: without it the compiler compares the whole 64-bit w, three instructions more)
     const int same = imol == jmol ? same_i : 0;

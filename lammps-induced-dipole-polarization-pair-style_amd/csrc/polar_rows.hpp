@@ -23,7 +23,7 @@ static __global__ void k_pack(int n, const int *__restrict__ perm, const double 
                        const double *__restrict__ alpha, const int *__restrict__ mol, const double *__restrict__ mu0,
                        AtomRec *__restrict__ r0, AtomRec *__restrict__ r1, int *__restrict__ mol_s,
                        double4 *__restrict__ pos4, double4 *__restrict__ xq_s, int wrap, Box box, double lo0, double lo1,
-                       double lo2) {
+                       double lo2, int keep_inert) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == n) {  // the DUMMY record the lp sweep pads its rows with: zero dipole (contributes nothing), zero
     // polarizability, a finite position (that of atom 0: the sweep floors r^2, so a coincidence is harmless)
@@ -51,8 +51,10 @@ static __global__ void k_pack(int n, const int *__restrict__ perm, const double 
   r0[i] = r;
   r1[i] = r;
   mol_s[i] = mol[o];
-  // 32-byte {x, y, z, (molecule id, alpha != 0)} for the list build
-  if (pos4) pos4[i] = make_double4(r.x, r.y, r.z, __hiloint2double(mol[o], r.a != 0.0 ? 1 : 0));
+  // 32-byte {x, y, z, (molecule id, kind of site)} for the list build.  The kind is worked out from the resident q and alpha
+  // every step (polar_set_atoms may change either); `keep_inert` (POLAR_NL_INERT=0) files the inert sites under SITE_CHARGED,
+  // which keeps them in every row of the full list
+  if (pos4) pos4[i] = make_double4(r.x, r.y, r.z, __hiloint2double(mol[o], r.a != 0.0 ? SITE_POLAR : ((site_is_inert(r.q, r.a) && !keep_inert) ? SITE_INERT : SITE_CHARGED)));
   if (xq_s) xq_s[i] = make_double4(r.x, r.y, r.z, r.q);  // 32-byte {x, y, z, q} for the static-field rows
 }
 
@@ -334,6 +336,25 @@ static __global__ void k_lj_walk_sum(int nrows, const int *__restrict__ walk, un
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off, 64);
   if ((threadIdx.x & 63) == 0 && w) atomicAdd(sum, (unsigned long long)w);
+}
+
+// polar_pair_extract "nl_entries" / "force_rows" (run when asked for, not per step): sum[0] += the entries the last list build
+// wrote into the full list, sum[1] += the rows of the last force launch whose atom is not inert.  The second is recomputed
+// here with the force kernel's own test (site_is_inert on the record's q and alpha), not counted by that kernel: it says how
+// many rows the launch had to walk, and cannot show that the launch skipped the others (its time does: DESIGN section 4).
+static __global__ void k_nl_inert_sums(int n, const int *__restrict__ nl_cnt, long long nl_pitch, int nrows, const int *__restrict__ rows,
+                                       const AtomRec *__restrict__ rec, unsigned long long *__restrict__ sum) {
+  long long e = 0, r = 0;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n || k < nrows; k += gridDim.x * blockDim.x) {
+    if (nl_cnt && k < n) e += nl_cnt[k] < nl_pitch ? nl_cnt[k] : nl_pitch;
+    if (k < nrows) { const int i = rows ? rows[k] : k; r += !site_is_inert(rec[i].q, rec[i].a); }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { e += __shfl_xor(e, off, 64); r += __shfl_xor(r, off, 64); }
+  if ((threadIdx.x & 63) == 0) {
+    if (e) atomicAdd(sum, (unsigned long long)e);
+    if (r) atomicAdd(sum + 1, (unsigned long long)r);
+  }
 }
 
 // One wave per listed atom i.  Per pair: 1 coalesced index load, two 16-byte gathers of {x,y,z,q},
@@ -700,13 +721,17 @@ static __device__ __forceinline__ void polar_force_body(const int *__restrict__ 
                                                              double ddcutsq, double pd, double e2s,
                                                              double *__restrict__ f, double *__restrict__ slots,
                                                              double *__restrict__ vatom, int vglobal, ExpCoef K,
-                                                             double *__restrict__ dbg6, double g_ewald POLAR_LIT_PARAM) {
+                                                             double *__restrict__ dbg6, double g_ewald, int skip_inert POLAR_LIT_PARAM) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * POLAR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (row >= nrows) return;
   const int i = rows ? rows[row] : row;
   const AtomRec *__restrict__ rec = __builtin_amdgcn_readfirstlane(scal_in->cur) ? recB : recA;  // scalar base
   const AtomRec ri = uniform_rec(rec[i]);  // row data is the same in every lane: scalar registers
+  // An inert row atom (no charge, no polarizability: an LJ-only site) has w = 0, eq = 0 and pol = false in its PairRow: every
+  // pair of its row adds an exact zero to every sum below (tests/test_inert_host.py), and u_self needs alpha != 0.  The wave
+  // leaves before its first list access; `debug yes` finds the zeros its buffer was cleared to.  (wave-uniform)
+  if (skip_inert && site_is_inert(ri.q, ri.a)) return;
   const int mi = mol[i];
   const PairRow pri = make_pair_row(ri.mx, ri.my, ri.mz, ri.q, ri.a, e2s);   // wave-uniform: scalar registers
   const PairCut cut{cut_coulsq, ddcutsq, -1.0 / cut_coulsq, pd};
@@ -809,16 +834,16 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_polar_force(
     const int *__restrict__ rows, int nrows, const int *__restrict__ perm, int nlocal, const Scal *scal_in,
     const AtomRec *__restrict__ recA, const AtomRec *__restrict__ recB, const int *__restrict__ mol, Box box, RowList nl,
     const int *__restrict__ nl_j, double cut_coulsq, double ddcutsq, double pd, double e2s, double *__restrict__ f,
-    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6 POLAR_LIT_PARAM) {
-  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, false>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, 0.0 POLAR_LIT_PASS);
+    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6, int skip_inert POLAR_LIT_PARAM) {
+  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, false>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, 0.0, skip_inert POLAR_LIT_PASS);
 }
 template <bool ALLPAIRS, int DAMP, bool EFLAG, bool VPAIR>
 static __global__ __launch_bounds__(POLAR_BLOCK) void k_ew_polar_force(
     const int *__restrict__ rows, int nrows, const int *__restrict__ perm, int nlocal, const Scal *scal_in,
     const AtomRec *__restrict__ recA, const AtomRec *__restrict__ recB, const int *__restrict__ mol, Box box, RowList nl,
     const int *__restrict__ nl_j, double cut_coulsq, double ddcutsq, double pd, double e2s, double *__restrict__ f,
-    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6, double g_ewald POLAR_LIT_PARAM) {
-  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, true>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, g_ewald POLAR_LIT_PASS);
+    double *__restrict__ slots, double *__restrict__ vatom, int vglobal, ExpCoef K, double *__restrict__ dbg6, double g_ewald, int skip_inert POLAR_LIT_PARAM) {
+  polar_force_body<ALLPAIRS, DAMP, EFLAG, VPAIR, true>(rows, nrows, perm, nlocal, scal_in, recA, recB, mol, box, nl, nl_j, cut_coulsq, ddcutsq, pd, e2s, f, slots, vatom, vglobal, K, dbg6, g_ewald, skip_inert POLAR_LIT_PASS);
 }
 
 static __global__ void k_add_into(long long n, const double *__restrict__ src, double *__restrict__ dst) {

@@ -396,11 +396,12 @@ void launch_force(polar_handle *h, int eflag, int vglobal, double *vatom, double
   if (ew) k_ew_polar_force<AP, DAMP, E, V><<<grid, block, 0, h->stream>>>(own_rows(h), own_n(h), h->sorted ? h->d_perm.p : nullptr, h->nlocal, h->d_scal.p, h->d_rec0.p, h->d_rec1.p,  \
                                                                h->d_mol_s.p, h->box, RowList{h->d_nl_cnt.p, h->nl_pitch}, h->d_nl_j.p,  \
                                                                ccs, dds, st.polar_damp, e2s, fdst, h->d_slots.p, vatom, vglobal, make_expcoef(),  \
-                                                               dbg6, g POLAR_LIT_ARG);                          \
+                                                               dbg6, g, h->nl_inert POLAR_LIT_ARG);             \
   else k_polar_force<AP, DAMP, E, V><<<grid, block, 0, h->stream>>>(own_rows(h), own_n(h), h->sorted ? h->d_perm.p : nullptr, h->nlocal, h->d_scal.p, h->d_rec0.p, h->d_rec1.p,  \
                                                                h->d_mol_s.p, h->box, RowList{h->d_nl_cnt.p, h->nl_pitch}, h->d_nl_j.p,  \
                                                                ccs, dds, st.polar_damp, e2s, fdst, h->d_slots.p, vatom, vglobal, make_expcoef(),  \
-                                                               dbg6 POLAR_LIT_ARG)
+                                                               dbg6, h->nl_inert POLAR_LIT_ARG)
+  h->force_ran = true; h->force_listed = !AP; h->force_nrows = own_n(h);   // (polar_pair_extract "force_rows")
   if (eflag) { if (vpair) { LF(true, true); } else { LF(true, false); } }
   else       { if (vpair) { LF(false, true); } else { LF(false, false); } }
 #undef LF
@@ -907,7 +908,7 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
   if (!ap) { build_cells(h); h->d_pos4.ensure(n + 1); if (h->static_xq) h->d_xq_s.ensure(n + 2); }  // cell order: perm / inv
   k_pack<<<nblk(n + 1, 256), 256, 0, s>>>(n, h->sorted ? h->d_perm.p : nullptr, h->d_x.p, h->d_q.p, h->d_alpha.p, h->d_mol.p, mu0,
                                       h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, ap ? nullptr : h->d_pos4.p, (!ap && h->static_xq) ? h->d_xq_s.p : nullptr,
-                                      (!ap && h->sweep_kernel == 4) ? 1 : 0, h->box, h->boxlo[0], h->boxlo[1], h->boxlo[2]);
+                                      (!ap && h->sweep_kernel == 4) ? 1 : 0, h->box, h->boxlo[0], h->boxlo[1], h->boxlo[2], h->nl_inert ? 0 : 1);
   if (!ap) {
     if (h->colors_valid && h->sweep_kernel < 3) map_color_rows(h);  // the colour rows in this step's cell order
     if (h->sweep_kernel == 2) compute_slots(h);
