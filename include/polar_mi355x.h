@@ -288,6 +288,46 @@ int polar_download(polar_handle *h, const char *name, double *dst, long long n);
 /* overwrite the device-resident dipoles (multi-GPU halo, use_previous across steps) */
 int polar_upload_mu(polar_handle *h, const double *mu, long long n);
 
+/* ---- the polarized box seen from arbitrary points (extension, not in the reference) ---------
+ * Field and potential, at npoints points x, of the charges and of the induced dipoles the last compute left -- the style's own
+ * rules, evaluated by the library instead of a host loop over downloaded dipoles.  With d = x_p - x_j (the image the mode's
+ * atom loops take: Domain::closest_image in exact mode, the list mode's rounded image there, tilted boxes included), r = |d|,
+ * e2s = sqrt(qqrd2e), rc = cut_coul and s3, s5 the style's tensor scalars (PS.cpp:1287-1297: damp1 / r^3 and 3 damp2 / r^5;
+ * with damping `none` 1 / r^3 and 3 / r^5):
+ *   e_static[3]   = e2s sum_j q_j (1/r^2 - 1/rc^2) d / r   over r^2 <= rc^2 and the molecule rule: the sum of the static
+ *                   field (PS.cpp:324-361), in the units of ef_static
+ *   phi_static    = e2s sum_j q_j (1/r + r/rc^2 - 2/rc)    over the same atoms: -grad phi_static = e_static, zero at rc
+ *   e_induced[3]  = -sum_j (s3 mu_j - s5 (mu_j.d) d)       exact mode: every minimum-image atom; list mode: r^2 < dd_cutoff^2
+ *                   (strict, as the sweep); no molecule rule (PS.cpp:512-602 has none)
+ *   phi_induced   = sum_j s3 (mu_j.d)                      over the same atoms: -grad phi_induced = e_induced
+ * mu_j = 0 where alpha_j == 0; an atom at r == 0 adds nothing.  Units: a test charge q_t at p has the energy
+ * q_t e2s (phi_static + phi_induced), a test polarizability alpha_t the first-order induction energy
+ * -1/2 alpha_t |e_static + e_induced|^2, both in LAMMPS energy units.
+ * Per point (either array may be NULL = none): skip_atom[p] = an atom (the caller's index, 0 .. nlocal-1) that adds nothing
+ * to any of the four, or -1; molecule[p] = a molecule id whose atoms are left out of the two STATIC sums by the style's rule
+ * (mol_p != mol_j || mol_p == 0), or 0.  With both set to atom i's, a point on atom i sees what atom i sees: e_static =
+ * ef_static[i], alpha_i (e_static + e_induced) = mu[i] of a converged solve.
+ * Any output may be NULL; without both potentials the kernel does not compute them.  device_ms (may be NULL): device time of
+ * the call's kernels, milliseconds.  All pointers are host pointers; synchronous on return.  The points are processed in
+ * passes of POLAR_FIELD_AT_CHUNK points (environment, read at every call; default 1048576), so device memory does not grow
+ * with the grid; a point's result does not depend on the pass it ran in, on the other points or on their order (no
+ * atomics), and the handle is not disturbed: the next compute gives the bits it would have given without the call.
+ * Points outside a periodic box wrap: whole lattice vectors are taken off a point once, in closed form, before the mode's
+ * image rule sees it, so the cost of a point does not depend on where it lies.  A point further than 2^30 box lengths from the
+ * box along a periodic direction is refused (POLAR_ERR_INPUT): its coordinate has too few digits left to place it in the box.
+ * npoints == 0 is a no-op.
+ * Valid after polar_compute / polar_compute_peratom / polar_compute_resident / polar_step_finish on a single unsharded handle,
+ * until the next polar_set_atoms, polar_set_positions*, polar_set_box, polar_set_settings, pair_style text call,
+ * polar_pair_init / polar_set_coul (qqrd2e scales the static sums), polar_mu_scatter* / polar_step_mu_put_idx (they rewrite
+ * the records' dipoles) or the start of the next step: POLAR_ERR_STATE outside that window.  The pass buffers (100 bytes per
+ * point of a pass) are freed when the next step begins.  POLAR_ERR_UNSUPPORTED with polar_ewald > 0 (the static field is not
+ * the shifted-force one there), on a row-sharded handle, with the lab build's tile sweep, and in list mode (dd_cutoff > 0) in
+ * a box with a non-periodic direction (exact mode takes such boxes).  POLAR_ERR_INPUT for a non-finite coordinate, a point
+ * beyond the limit above, a skip_atom outside [-1, nlocal), npoints < 0. */
+int polar_field_at(polar_handle *h, long long npoints, const double *x /*[npoints][3]*/, const int *skip_atom,
+                   const int *molecule, double *e_static, double *e_induced /* [npoints][3] each */,
+                   double *phi_static, double *phi_induced /* [npoints] each */, double *device_ms);
+
 
 /* ---- stepwise / sharded interface (multi-GPU driver: one process per GPU, rows sharded) ------
  * The reference is single-process only (README.md:5; its pack_comm/unpack_comm are dead code,

@@ -139,6 +139,7 @@ EXPORTS = {
     "polar_dev_ptr": (C.c_void_p, [C.c_void_p, C.c_char_p]),
     "polar_download": (C.c_int, [C.c_void_p, C.c_char_p, _dp, C.c_longlong]),
     "polar_upload_mu": (C.c_int, [C.c_void_p, _dp, C.c_longlong]),
+    "polar_field_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "polar_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "polar_set_row_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "polar_set_global_count": (C.c_int, [C.c_void_p, C.c_longlong]),
@@ -338,6 +339,7 @@ class PolarPair:
         lo, pr, ti = (np.asarray(v, dtype=np.float64) for v in (boxlo, prd, tilt))
         pe = np.asarray(periodic, dtype=np.int32)
         self._ck(self.L.polar_set_box(self.h, _dptr(lo), _dptr(pr), _dptr(ti), _iptr(pe), triclinic))
+        self._box = (lo.copy(), pr.copy(), ti.copy() if triclinic else np.zeros(3))   # (grid_points)
 
     def set_atoms(self, nlocal, nghost, x, q, alpha, typ, mol):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -479,6 +481,48 @@ class PolarPair:
         rc = self._ck(self.L.polar_compute_resident(self.h, eflag, vflag, C.byref(res)))
         out = _result_dict(res)
         out.update(status=rc, warning=self.L.polar_last_warning(self.h).decode())
+        return out
+
+    # ---- the polarized box seen from arbitrary points ----
+    def field_at(self, x, skip_atom=None, molecule=None, potential=True):
+        """Field and potential of the charges and of the induced dipoles of the last compute at the points ``x`` [m, 3]
+        (polar_field_at in include/polar_mi355x.h: formulas, units, when the call is valid).  ``skip_atom`` [m]: an atom
+        index per point that contributes nothing, or -1; ``molecule`` [m]: a molecule id per point whose atoms are left out
+        of the static sums, or 0.  Returns a dict: e_static, e_induced [m, 3], phi_static, phi_induced [m] (None without
+        ``potential``), ms (device time of the kernels)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        m = len(x)
+        sk = None if skip_atom is None else np.ascontiguousarray(skip_atom, dtype=np.int32)
+        mo = None if molecule is None else np.ascontiguousarray(molecule, dtype=np.int32)
+        assert (sk is None or sk.shape == (m,)) and (mo is None or mo.shape == (m,))
+        es, ei = np.zeros((m, 3)), np.zeros((m, 3))
+        ps, pi = (np.zeros(m), np.zeros(m)) if potential else (None, None)
+        ms = C.c_double()
+        self._ck(self.L.polar_field_at(self.h, m, _dptr(x), None if sk is None else _iptr(sk), None if mo is None else _iptr(mo),
+                                       _dptr(es), _dptr(ei), None if ps is None else _dptr(ps), None if pi is None else _dptr(pi),
+                                       C.byref(ms)))
+        return dict(e_static=es, e_induced=ei, phi_static=ps, phi_induced=pi, ms=ms.value)
+
+    def grid_points(self, shape):
+        """The points of ``field_grid``: cell-centred fractional coordinates ((i + 1/2) / nx, (j + 1/2) / ny, (k + 1/2) / nz) of
+        the box of the last ``set_box``, tilted boxes included, x running fastest.  [nx * ny * nz, 3]."""
+        nx, ny, nz = (int(v) for v in shape)
+        lo, prd, tilt = self._box
+        fz, fy, fx = np.meshgrid((np.arange(nz) + 0.5) / nz, (np.arange(ny) + 0.5) / ny, (np.arange(nx) + 0.5) / nx, indexing="ij")
+        fx, fy, fz = fx.ravel(), fy.ravel(), fz.ravel()
+        xy, xz, yz = tilt
+        return np.stack([lo[0] + fx * prd[0] + fy * xy + fz * xz, lo[1] + fy * prd[1] + fz * yz, lo[2] + fz * prd[2]], axis=1)
+
+    def field_grid(self, shape, potential=True):
+        """``field_at`` on an (nx, ny, nz) grid of cell-centred points of the handle's box (``grid_points``).  x runs fastest,
+        so consecutive points are neighbours; the arrays come back as (nz, ny, nx[, 3])."""
+        nx, ny, nz = (int(v) for v in shape)
+        out = self.field_at(self.grid_points((nx, ny, nz)), potential=potential)
+        for k in ("e_static", "e_induced"):
+            out[k] = out[k].reshape(nz, ny, nx, 3)
+        for k in ("phi_static", "phi_induced"):
+            if out[k] is not None:
+                out[k] = out[k].reshape(nz, ny, nx)
         return out
 
     def debug_trace(self, nmax=1024):

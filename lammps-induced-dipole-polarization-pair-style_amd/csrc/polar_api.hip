@@ -265,6 +265,7 @@ int polar_pair_init(polar_handle *h, double g_ewald, double qqrd2e, const double
     PairHost &p = h->ph;
     p.init(g_ewald, qqrd2e, special_lj, special_coul);
     h->coul_set = false;
+    h->field_ready = false;   // (qqrd2e scales polar_field_at's static sums: they belong to the step that was computed with it)
     if (h->have_device) {
       HIPCHECK(hipSetDevice(h->device));
       const double *t[7] = {p.lj1.data(), p.lj2.data(), p.lj3.data(), p.lj4.data(), p.offset.data(), p.cut_ljsq.data(), p.cutsq.data()};
@@ -347,6 +348,7 @@ int polar_set_settings(polar_handle *h, const polar_settings *s) {
     if (!(v.polar_ewald >= 0.0 && v.polar_ewald < 1.0)) throw InputError("polar_ewald must lie in [0, 1)");
     h->ph.st = v;
     h->colors_valid = false;
+    h->field_ready = false;
     return POLAR_OK;
   });
 }
@@ -366,6 +368,7 @@ int polar_set_coul(polar_handle *h, double g_ewald, double qqrd2e, const double 
   return guarded(h, [&]() {
     const double *c[8] = {rtable, drtable, ftable, dftable, ctable, dctable, etable, detable};
     h->ph.set_tables(nbits, mask, shift, tabinnersq, c);  // host copy: polar_pair_single reads the same table
+    h->field_ready = false;   // (qqrd2e, as in polar_pair_init)
     h->ph.g_ewald = g_ewald; h->ph.qqrd2e = qqrd2e;
     for (int k = 0; k < 4; k++) { h->ph.special_lj[k] = special_lj[k]; h->ph.special_coul[k] = special_coul[k]; }
     if (h->have_device) {
@@ -399,6 +402,7 @@ int polar_set_box(polar_handle *h, const double boxlo[3], const double prd[3], c
     same = same && h->box.triclinic == nb.triclinic && h->box.xy == nb.xy && h->box.xz == nb.xz && h->box.yz == nb.yz;
     h->box = nb;
     h->box_set = true;
+    h->field_ready = false;   // (polar_field_at: the records belong to the box they were made in)
     // a shim hands the box over every step: the colour phases (host-side colouring, rank metric) are rebuilt only when
     // the box really changed -- and on reneighbor steps, through polar_set_neighbors* / polar_build_neighbors
     if (!same) h->colors_valid = false;
@@ -413,6 +417,7 @@ int polar_set_atoms(polar_handle *h, int nlocal, int nghost, const double *x, co
     HIPCHECK(hipSetDevice(h->device));
     if (nlocal < 0 || nghost < 0) throw InputError("negative atom count");
     h->force_ran = false;   // "nl_entries" / "force_rows" describe a compute call on THESE atoms: 0 until the next one (inert_counters)
+    h->field_ready = false;
     const size_t nall = (size_t)nlocal + nghost;
     // the checks and the copies into the pinned staging area by the helper threads (a reneighbor step of an MD run hands all
     // five arrays over: single-threaded checks + five copies out of pageable memory cost 1.3 ms at 258k atoms)
@@ -475,6 +480,7 @@ int polar_set_positions(polar_handle *h, int nlocal, int nghost, const double *x
     HIPCHECK(hipSetDevice(h->device));
     if (!h->atoms_set || nlocal != h->nlocal || nghost != h->nghost) throw InputError("polar_set_positions: atom counts differ from the last polar_set_atoms");
     if (!x) throw InputError("polar_set_positions: null pointer");
+    h->field_ready = false;
     const size_t nall = (size_t)nlocal + nghost;
     // through the pinned staging area: a pageable source is staged by the runtime in small pieces at a third of the rate
     // (the caller's array is NOT registered in place, as VERDICT r2 suggested: a registration outlives a free + malloc that
@@ -652,6 +658,7 @@ int polar_compute(polar_handle *h, int eflag, int vflag, double *f, double *mu, 
     }
     lap("f arrived and added");
     h->mu_host_in_sync = true;
+    h->field_ready = true;
     return rc;
   });
 }
@@ -677,6 +684,7 @@ int polar_compute_peratom(polar_handle *h, int eflag, int vflag, double *f, doub
     HIPCHECK(hipMemcpy(mu, h->d_mu.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
     if (ef_static) HIPCHECK(hipMemcpy(ef_static, h->d_ef.p, 3 * n * sizeof(double), hipMemcpyDeviceToHost));
     h->mu_host_in_sync = true;
+    h->field_ready = true;
     return rc;
   });
 }
@@ -686,7 +694,9 @@ int polar_compute_resident(polar_handle *h, int eflag, int vflag, polar_result *
     if (!out) throw std::runtime_error("polar_compute_resident: null result pointer");
     need_device(h);
     HIPCHECK(hipSetDevice(h->device));
-    return do_compute(h, eflag, vflag, nullptr, out);
+    const int rc = do_compute(h, eflag, vflag, nullptr, out);
+    if (rc >= 0) h->field_ready = true;
+    return rc;
   });
 }
 
@@ -716,6 +726,38 @@ int polar_upload_mu(polar_handle *h, const double *mu, long long n) {
     HIPCHECK(hipMemcpy(h->d_mu.p, mu, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
     h->mu_resident = true;
     return POLAR_OK;
+  });
+}
+
+/* ---- field and potential of the polarized box at arbitrary points (polar_field_at.hpp) -------- */
+int polar_field_at(polar_handle *h, long long npoints, const double *x, const int *skip_atom, const int *molecule,
+                   double *e_static, double *e_induced, double *phi_static, double *phi_induced, double *device_ms) {
+  return guarded(h, [&]() {
+    need_device(h);
+    const polar_settings &st = h->ph.st;
+    if (ewald_on(h)) throw Unsupported("polar_field_at: with polar_ewald the static field is not the shifted-force one");
+    if (sharded(h)) throw Unsupported("polar_field_at: not offered on a row-sharded handle");
+    if (tile_mode(h)) throw Unsupported("polar_field_at: not offered with the tile sweep (lab build)");
+    if (!h->field_ready) throw std::runtime_error("polar_field_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
+    if (st.dd_cutoff > 0.0 && !(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2]))
+      throw Unsupported("polar_field_at: list mode (dd_cutoff > 0) needs a box periodic in every direction");
+    if (npoints < 0) throw InputError("polar_field_at: negative point count");
+    if (device_ms) *device_ms = 0.0;
+    if (npoints == 0) return (int)POLAR_OK;
+    if (!x) throw InputError("polar_field_at: null pointer");
+    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
+    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    HIPCHECK(hipSetDevice(h->device));
+    // read at every call: a pass holds at most this many points on the device
+    const char *e = getenv("POLAR_FIELD_AT_CHUNK");
+    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
+    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
+      const int m = (int)std::min(chunk, npoints - p0);
+      field_at_pass(h, m, x + 3 * p0, skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr,
+                    e_static ? e_static + 3 * p0 : nullptr, e_induced ? e_induced + 3 * p0 : nullptr,
+                    phi_static ? phi_static + p0 : nullptr, phi_induced ? phi_induced + p0 : nullptr, device_ms);
+    }
+    return (int)POLAR_OK;
   });
 }
 
@@ -828,6 +870,7 @@ int polar_set_positions_range(polar_handle *h, int lo, int hi, const double *x) 
     HIPCHECK(hipSetDevice(h->device));
     if (!h->atoms_set || lo < 0 || hi < lo || hi > h->nlocal + h->nghost) throw InputError("polar_set_positions_range: range outside the atoms of the last polar_set_atoms");
     if (hi > lo && !x) throw InputError("polar_set_positions_range: null pointer");
+    h->field_ready = false;
     const size_t cnt = 3 * (size_t)(hi - lo);
     double *st = staging(h, 3 * ((size_t)h->nlocal + h->nghost) + 6 * (size_t)h->nlocal);
     if (cnt) {
@@ -899,6 +942,7 @@ int polar_step_finish(polar_handle *h, polar_result *out) {
       h->warn = "neighbor list pitch overflow: pitch enlarged, repeat the step";
       return POLAR_RETRY_STEP;
     }
+    h->field_ready = true;
     return rc;
   });
 }
@@ -912,6 +956,7 @@ int polar_mu_gather(polar_handle *h, long long lo, long long hi, double *dev_dst
 int polar_mu_scatter(polar_handle *h, long long lo, long long hi, const double *dev_src) {
   return guarded(h, [&]() {
     need_device(h);
+    h->field_ready = false;   // (the records' dipoles are no longer those of the finished step)
     if (hi > lo) k_mu_scatter<<<nblk(hi - lo, 256), 256, 0, h->stream>>>(lo, hi, h->sorted ? h->d_inv.p : nullptr, h->d_scal.p, mu_view(h), dev_src);
     return POLAR_OK;
   });
@@ -926,6 +971,7 @@ int polar_mu_gather_idx(polar_handle *h, const int *dev_idx, long long n, double
 int polar_mu_scatter_idx(polar_handle *h, const int *dev_idx, long long n, const double *dev_src) {
   return guarded(h, [&]() {
     need_device(h);
+    h->field_ready = false;
     if (n > 0) k_mu_scatter_idx<<<nblk(n, 256), 256, 0, h->stream>>>(n, dev_idx, h->sorted ? h->d_inv.p : nullptr, h->d_scal.p, mu_view(h), dev_src, own_lo(h), own_lo(h) + own_n(h));
     return POLAR_OK;
   });
@@ -956,6 +1002,7 @@ int polar_step_mu_put_idx(polar_handle *h, long long n, const int *idx_host, con
     need_device(h);
     if (n < 0 || (n > 0 && (!idx_host || !mu_host))) throw InputError("polar_step_mu_put_idx: null pointer");
     if (n == 0) return (int)POLAR_OK;
+    h->field_ready = false;
     for (long long k = 0; k < n; k++)
       if (idx_host[k] >= h->nlocal) throw InputError("polar_step_mu_put_idx: atom index out of range");
     h->d_xchg.ensure(3 * (size_t)n); h->d_xidx.ensure((size_t)n);

@@ -308,6 +308,13 @@ struct polar_handle {
   double ew_cell[6] = {0, 0, 0, 0, 0, 0};
   Event ev_ks[4];
   int ntrace = 0;
+  // polar_field_at (polar_field_at.hpp): the records, the cell table and the molecule ids on the device are those of a finished
+  // step (set by the compute calls and polar_step_finish, cleared by every setter that moves atoms, box or settings and by
+  // the start of a step); one pass's points {x | skip_atom, molecule} and its results, the events around its kernel
+  bool field_ready = false;
+  DBuf<double> d_fa_x, d_fa_out;
+  DBuf<int> d_fa_idx;
+  Event ev_fa[2];
   // Everything above frees itself.  What is left to do first: let the device finish with it.
   ~polar_handle() {
     if (!device_set) return;
@@ -316,7 +323,7 @@ struct polar_handle {
       if (s) (void)hipStreamSynchronize(s);
   }
   // the settings changed: the colour phases and every list pitch are made again
-  void reset_plan() { colors_valid = false; nl_pitch = dd_pitch = 0; cl_pitch = 0; un_pitch = 0; pitch16 = 0; }
+  void reset_plan() { field_ready = false; colors_valid = false; nl_pitch = dd_pitch = 0; cl_pitch = 0; un_pitch = 0; pitch16 = 0; }
 };
 inline int fail(polar_handle *h, int code, const std::string &m) {
   if (h) h->err = m;
@@ -503,6 +510,10 @@ void step_begin_lists(polar_handle *h, int eflag, int vflag);   // polar_step_be
 bool step_needs_colors(const polar_handle *h);
 void step_begin_finish(polar_handle *h);                        // ... and from there on (rows into launch order, descriptors)
 void build_cluster_lists(polar_handle *h);
+// one pass of polar_field_at: m points (host arrays; skip_atom, molecule and every output may be null), the kernel's device
+// time added to *ms; synchronous on return
+void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
+                   double *e_induced, double *phi_static, double *phi_induced, double *ms);
 // ---- polar_color.hip --------------------------------------------------------------------------------------------------
 void ensure_colors(polar_handle *h);
 struct ColorComm {   // what a distributed colouring needs from the transport (polar_dist.hip)

@@ -38,6 +38,37 @@ inline bool scan_positions(const double *src, double *dst, size_t a0, size_t a1,
   return acc == 0.0;   // (v - v is 0 for a finite v, NaN for an infinite or NaN one)
 }
 
+// ---- polar_field_at ---------------------------------------------------------------------------------------------------------
+// The points of a call: every coordinate finite, no point further than POLAR_FIELD_AT_MAX_IMAGES box lengths from the box along
+// a periodic direction (fractional coordinates as Domain::x2lamda forms them; tilt = {xy, xz, yz} or null), every skip_atom
+// (may be null) -1 or an atom of the handle.  The kernel takes whole lattice vectors off a point once, in closed form, before
+// any image rule sees it: inside the limit what is left lies in the box to 2^-22 of a box length, so the add / subtract loops of
+// closest_image (exact mode) run as they do for an atom.  Beyond it a coordinate has too few digits left to say where in the box
+// the point is -- a grid made from a wrong box, garbage -- and is refused instead of mapped somewhere.
+#define POLAR_FIELD_AT_MAX_IMAGES 1073741824.0   // 2^30
+inline void check_points(long long npoints, const double *x, const int *skip_atom, int nlocal, const double lo[3], const double prd[3],
+                         const double *tilt, const int periodic[3]) {
+  double acc = 0.0;
+  for (long long k = 0; k < 3 * npoints; k++) acc += x[k] - x[k];
+  if (!(acc == 0.0)) throw InputError("polar_field_at: non-finite coordinate");
+  const double xy = tilt ? tilt[0] : 0.0, xz = tilt ? tilt[1] : 0.0, yz = tilt ? tilt[2] : 0.0;
+  for (long long p = 0; p < npoints; p++) {
+    const double f2 = (x[3 * p + 2] - lo[2]) / prd[2];
+    const double f1 = ((x[3 * p + 1] - lo[1]) - yz * f2) / prd[1];
+    const double f0 = ((x[3 * p] - lo[0]) - xy * f1 - xz * f2) / prd[0];
+    const bool far = (periodic[2] && std::fabs(f2) > POLAR_FIELD_AT_MAX_IMAGES) || (periodic[1] && std::fabs(f1) > POLAR_FIELD_AT_MAX_IMAGES) ||
+                     (periodic[0] && std::fabs(f0) > POLAR_FIELD_AT_MAX_IMAGES);
+    if (far || !std::isfinite(f0) || !std::isfinite(f1) || !std::isfinite(f2))
+      throw InputError("polar_field_at: point further than 2^30 box lengths from the box");
+  }
+  if (skip_atom)
+    for (long long p = 0; p < npoints; p++)
+      if (skip_atom[p] < -1 || skip_atom[p] >= nlocal) throw InputError("polar_field_at: skip_atom outside [-1, nlocal)");
+}
+// Points per pass from POLAR_FIELD_AT_CHUNK (0 or negative: not set or nonsense -> the default 2^20); at most 2^24, so that a
+// pass's buffers (100 bytes per point) stay below 2 GB
+inline long long field_at_chunk(long long env) { return env <= 0 ? (1ll << 20) : std::min(env, 1ll << 24); }
+
 // ---- pair tables ----------------------------------------------------------------------------------------------------------
 // The LJ tables repacked so that the half-list loop reads one 64-byte line per type pair:
 // t = lj1, lj2, lj3, lj4, offset, cut_ljsq, cutsq  ->  cutsq, cut_ljsq, lj1, lj2, lj3, lj4, offset, pad.

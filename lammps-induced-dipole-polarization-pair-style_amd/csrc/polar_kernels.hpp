@@ -22,7 +22,8 @@
 // polar_exact.hpp (exact mode's exact-order Gauss-Seidel), polar_accel.hpp (Anderson mixing, `polar_accel`),
 // polar_lists.hpp (list mode: cells, neighbor lists, exchange), polar_tiles.hpp (list mode: the tile sweep
 // -- one workgroup per cell, neighbour records staged in LDS -- and its builder), polar_ewald.hpp (`polar_ewald`: the
-// reciprocal-space static field and charge-dipole forces).
+// reciprocal-space static field and charge-dipole forces); and polar_field_at.hpp (`polar_field_at`: field and potential of the
+// polarized box at arbitrary points, one wave per point; its pair arithmetic in the plain-C++ polar_point_pair.hpp).
 #pragma once
 
 #include "polar_common.hpp"
@@ -33,3 +34,4 @@
 #include "polar_lists.hpp"
 #include "polar_tiles.hpp"
 #include "polar_ewald.hpp"
+#include "polar_field_at.hpp"   // the field and the potential of the polarized box at arbitrary points (polar_field_at)

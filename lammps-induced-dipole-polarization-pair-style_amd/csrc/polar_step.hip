@@ -718,6 +718,8 @@ void solve(polar_handle *h, bool ap, polar_result *out) {
 // PS.cpp:125-386: everything before the solve
 void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
   need_device(h);
+  h->field_ready = false;   // (polar_field_at: the records are being rewritten until the step has finished)
+  h->d_fa_x.release(); h->d_fa_idx.release(); h->d_fa_out.release();   // a probe's pass buffers (100 bytes per point) do not outlive the step it looked at
   if (!h->types_set || !h->coul_set) throw std::runtime_error("polar_compute before the pair tables were set: polar_pair_init (or polar_set_types), then polar_set_coul with the Coulomb tables of Pair::init_tables unless pair_modify table 0");
   if (!h->box_set || !h->atoms_set || !h->neigh_set) throw std::runtime_error("polar_compute before polar_set_box/polar_set_atoms/polar_set_neighbors");
   const polar_settings &st = h->ph.st;
@@ -1141,4 +1143,52 @@ void step_begin_finish(polar_handle *h) {
   if (!st.zodid && st.dd_cutoff > 0.0 && (st.polar_gs || st.polar_gs_ranked) && h->sweep_kernel == 2 && !slots_current(h)) { compute_slots(h); build_lists(h); }
   if (!st.zodid && st.dd_cutoff > 0.0 && h->sweep_kernel == 2) prepare_lp(h);
   h->in_step = true;
+}
+
+// polar_field_at, one pass: the points go up, one launch of k_field_at (polar_field_at.hpp) on the handle's stream reads the
+// records, the molecule ids and -- list mode -- the cell table the finished step left, the results the caller asked for come
+// back.  Nothing of the handle's step state is written.
+void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
+                   double *e_induced, double *phi_static, double *phi_induced, double *ms) {
+  const polar_settings &st = h->ph.st;
+  const bool ap = !(st.dd_cutoff > 0.0);
+  const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
+  const bool phi = phi_static || phi_induced;
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fa_out.ensure(8 * mm);
+  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
+  HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
+  int *d_skip = nullptr, *d_pmol = nullptr;
+  if (skip_atom) { d_skip = h->d_fa_idx.p; HIPCHECK(hipMemcpyAsync(d_skip, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  if (molecule) { d_pmol = h->d_fa_idx.p + mm; HIPCHECK(hipMemcpyAsync(d_pmol, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  const double rc = st.cut_coul;
+  const PointCut cut{rc * rc, st.dd_cutoff * st.dd_cutoff, 1.0 / (rc * rc), 2.0 / rc, st.polar_damp};
+  double *o = h->d_fa_out.p;
+  const FieldAtOut out{o};
+  const double e2s = std::sqrt(h->P.qqrd2e);
+  const ExpCoef K = make_expcoef();
+  CellGrid cg = h->grid;   // (exact mode has built no grid: the kernel takes the box origin from it in both modes)
+  for (int k = 0; k < 3; k++) cg.lo[k] = h->boxlo[k];
+  const dim3 grid(nblk(m, POLAR_ROWS_PER_BLOCK)), block(POLAR_BLOCK);
+  HIPCHECK(hipEventRecord(h->ev_fa[0], s));
+#define FA(AP, D, P)                                                                                                          \
+  k_field_at<AP, D, P><<<grid, block, 0, s>>>(m, h->d_fa_x.p, d_skip, d_pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,    \
+                                              h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, cg,                \
+                                              AP ? nullptr : h->d_cell_first.p, cut, e2s, K, out)
+#define FAP(AP, D) do { if (phi) FA(AP, D, true); else FA(AP, D, false); } while (0)
+  if (ap) { if (expd) FAP(true, 0); else FAP(true, 1); }
+  else    { if (expd) FAP(false, 0); else FAP(false, 1); }
+#undef FAP
+#undef FA
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa[1], s));
+  if (e_static) HIPCHECK(hipMemcpyAsync(e_static, out.es(), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (e_induced) HIPCHECK(hipMemcpyAsync(e_induced, out.ei(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (phi_static) HIPCHECK(hipMemcpyAsync(phi_static, out.ps(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (phi_induced) HIPCHECK(hipMemcpyAsync(phi_induced, out.pi(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  float t = 0.f;
+  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
+  if (ms) *ms += (double)t;
 }
