@@ -159,7 +159,11 @@ double polar_pair_single(const polar_handle *h, double qi, double qj, int itype,
  * polarization-force launch had to walk (every row whose atom is not such a site; worked out from the atoms' records by the
  * kernel's own test when asked for, not counted inside the launch).  Both read 0 again after polar_set_atoms or
  * polar_set_row_range, until the next compute call.  A handle created with POLAR_NL_INERT=0 in the
- * environment lists every partner and walks every row. */
+ * environment lists every partner and walks every row.
+ * "cell_active" (dim 0, a double, copied from the device when asked for; list mode, 0 before the first compute call): the
+ * atoms the last build of the cell order filed in the list grid's own bins -- the atoms that are not such sites, which come
+ * first in cell order; all atoms for a handle created with POLAR_CELL_INERT=0 or POLAR_NL_INERT=0, which keeps such sites
+ * between the others. */
 const void *polar_pair_extract(const polar_handle *h, const char *name, int *dim);
 int polar_get_settings(const polar_handle *h, polar_settings *out);
 

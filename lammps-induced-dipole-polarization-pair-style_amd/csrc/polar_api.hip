@@ -228,6 +228,7 @@ int polar_create(int device, polar_handle **out) {
     if (const char *e = getenv("POLAR_LJ_PERS")) h->lj_pers = atoi(e);
     if (const char *e = getenv("POLAR_LJ_SKIN")) h->lj_skin = atoi(e) != 0;   // 0: the LJ/Coulomb rows are walked whole (the A/B partner of the distance classes)
     if (const char *e = getenv("POLAR_NL_INERT")) h->nl_inert = atoi(e) != 0;   // 0: inert sites stay in the full list and keep their force rows (the A/B partner)
+    if (const char *e = getenv("POLAR_CELL_INERT")) h->cell_inert = atoi(e) != 0;   // 0: inert sites stay between the others in cell order (the split's A/B partner; no effect with POLAR_NL_INERT=0, which turns the split off too)
     if (const char *e = getenv("POLAR_LJ_PERS_THREADS")) h->lj_pers_threads = std::max(256, std::min(POLAR_LJ_PERS_THREADS, (atoi(e) / 64) * 64));
     { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess) h->ncu = ncu; }
     h->h_scal.ensure(1);
@@ -308,6 +309,22 @@ const void *polar_pair_extract(const polar_handle *h, const char *name, int *dim
     polar_handle *m = const_cast<polar_handle *>(h);
     if (guarded(m, [&]() { lj_counters(m); return POLAR_OK; }) != POLAR_OK) return nullptr;
     return name[3] == 'w' ? &h->lj_walked : &h->lj_entries;
+  }
+  // atoms the last cell build filed in the grid's own bins: all of them, or, with the inert sites behind the grid, the others
+  if (strcmp(name, "cell_active") == 0) {
+    polar_handle *m = const_cast<polar_handle *>(h);
+    m->cell_active = 0.0;
+    if (h->have_device && h->sorted && h->ph.st.dd_cutoff > 0.0 && h->ncell > 0 && h->d_cell_first.p) {   // (list mode, after a step)
+      long long v = 0;
+      if (guarded(m, [&]() {
+            HIPCHECK(hipSetDevice(m->device));
+            HIPCHECK(hipMemcpyAsync(&v, m->d_cell_first.p + m->ncell, sizeof(v), hipMemcpyDeviceToHost, m->stream));
+            HIPCHECK(hipStreamSynchronize(m->stream));
+            return POLAR_OK;
+          }) != POLAR_OK) return nullptr;
+      m->cell_active = (double)v;
+    }
+    return &h->cell_active;
   }
   // entries the last list build wrote into the full list / rows the last force launch walked (fewer than all partners and
   // all rows where the system holds inert sites: no charge, no polarizability)

@@ -137,6 +137,9 @@ struct polar_handle {
   double lj_walked = 0.0, lj_entries = 0.0;   // polar_pair_extract "lj_walked" / "lj_entries"
   // inert sites (q == 0 and alpha == 0, SITE_INERT in polar_common.hpp) are left out of the full list and their force rows are skipped
   int nl_inert = 1;         // POLAR_NL_INERT=0: every partner listed, every force row walked
+  int cell_inert = 1;       // POLAR_CELL_INERT=0: inert sites stay in their cells' bins instead of behind the grid (build_cells; the A/B partner of the split cell order)
+  bool cell_split = false;  // the cell order in force has the inert sites behind the grid
+  double cell_active = 0.0; // polar_pair_extract "cell_active": the atoms in the grid's own bins, cell_first[ncell], of the last build (0: none yet)
   bool force_ran = false, force_listed = false; int force_nrows = 0;   // the last force launch: list mode, its rows
   double nl_entries = 0.0, force_rows = 0.0;   // polar_pair_extract "nl_entries" / "force_rows"
   DBuf<unsigned long long> d_inert_sums;

@@ -5,6 +5,7 @@
 
 #include "polar_common.hpp"
 #include "polar_nl_dense.hpp"
+#include "polar_plan.hpp"   // cell_bin
 
 namespace polar {
 
@@ -30,11 +31,14 @@ __device__ __forceinline__ int cell_of(const CellGrid &g, const Box &b, double x
   return (c[2] * g.nc[1] + c[1]) * g.nc[0] + c[0];
 }
 
-static __global__ void k_cell_count(int n, const double *__restrict__ x, CellGrid g, Box b, int *__restrict__ cell_id,
-                             int *__restrict__ cell_cnt) {
+// cell_id[i] = the BIN of atom i (cell_bin, polar_plan.hpp): its cell, or -- `split_ncell` > 0, the number of cells -- the
+// cell's twin behind the grid for an inert site.  q and alpha are read here every step: polar_set_atoms may change either.
+static __global__ void k_cell_count(int n, const double *__restrict__ x, const double *__restrict__ q, const double *__restrict__ alpha,
+                             CellGrid g, Box b, long long split_ncell, int *__restrict__ cell_id, int *__restrict__ cell_cnt) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  int c = cell_of(g, b, x[3 * i], x[3 * i + 1], x[3 * i + 2]);
+  const int cell = cell_of(g, b, x[3 * i], x[3 * i + 1], x[3 * i + 2]);
+  const int c = (int)cell_bin(cell, split_ncell, split_ncell > 0 && site_is_inert(q[i], alpha[i]), split_ncell > 0);
   cell_id[i] = c;
   atomicAdd(&cell_cnt[c], 1);
 }
@@ -122,6 +126,8 @@ static __global__ __launch_bounds__(256) void k_scan_add(long long n, long long 
 // Inside a cell the polarizable atoms come first (filled from the front), the others last (from the back): the dipole lists
 // then hold long runs of CONSECUTIVE records -- gathers of neighbouring records merge into whole 128-byte lines and run
 // 20 % faster than scattered ones (tools/calib_gather48.hip: 246 against 203 G records/s from an L2-resident table).
+// `cell_id` holds bins, `cell_first` the scan over all of them: an inert bin (k_cell_count) has no polarizable atom and is
+// filled from the back alone.
 static __global__ void k_cell_fill(int n, const int *__restrict__ cell_id, const long long *__restrict__ cell_first,
                             int *__restrict__ fill, int *__restrict__ fill_back, const double *__restrict__ alpha,
                             int *__restrict__ perm, int *__restrict__ inv) {
@@ -138,6 +144,7 @@ static __global__ void k_cell_fill(int n, const int *__restrict__ cell_id, const
 // two groups (polarizable atoms, the others) into ascending atom index, so that every list -- and with it every
 // floating-point sum and the device colouring's tie-breaks -- has the same order run after run.  A lane holds one atom and
 // counts the smaller indices of its group (rank sort, ~20 entries); groups of more than 64 fall to a serial insertion sort.
+// (`ncell` = the bins of the counting sort: an inert bin is one group, its front group being empty.)
 static __global__ __launch_bounds__(256) void k_cell_sort(long long ncell, const long long *__restrict__ cell_first, const int *__restrict__ npol,
                                                    int *__restrict__ perm, int *__restrict__ inv) {
   const int lane = threadIdx.x & 63;
@@ -596,7 +603,11 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_nl_build(const int *__re
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * POLAR_ROWS_PER_BLOCK + (threadIdx.x >> 6);
   if (row >= nrows) return;
-  const int i = __builtin_amdgcn_readfirstlane(rows ? rows[row] : row);  // s space: the atoms of cell c are the indices [cell_first[c], cell_first[c+1])
+  // s space: [cell_first[c], cell_first[c+1]) holds the atoms of cell c that are not inert; its inert ones lie behind the
+  // grid, in bin ncell + c (build_cells), which no candidate walk visits -- every reader of the lists would add an exact zero
+  // for them.  An inert ROW atom still gets its row (the static field at the site): it finds its stencil from its position
+  // and is simply not among its own candidates.  (Split off, POLAR_CELL_INERT=0: every atom of cell c.)
+  const int i = __builtin_amdgcn_readfirstlane(rows ? rows[row] : row);
   const double4 ri = pos4[i];            // {x, y, z, (molecule, kind of site)}
   const int imol = __double2hiint(ri.w), ipol = __double2loint(ri.w) >= SITE_POLAR;
   // colour re-validation on reneighbor steps (color_s != NULL): the colouring of the previous list stays in use unless

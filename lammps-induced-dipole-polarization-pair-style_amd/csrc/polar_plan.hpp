@@ -50,6 +50,29 @@ inline bool list_grid(const double width[3], const int periodic[3], double cutal
   return true;
 }
 
+// ---- cell order: inert sites behind the grid ------------------------------------------------------------------------------
+// With the split on, the counting sort of build_cells runs over two copies of the list grid laid back to back: bin c holds
+// the sites of cell c that carry a charge or a polarizability, bin ncell + c its inert ones (q == 0 and alpha == 0:
+// site_is_inert, polar_common.hpp).  cell_first[0 .. ncell] then spans the active sites alone -- what every candidate walk
+// reads -- and the inert sites follow them in cell order.  Off: one copy, every site in its cell's bin.
+// (k_cell_count calls cell_bin on the device; everything else here is host arithmetic.)
+#if defined(__HIPCC__)
+#define POLAR_PLAN_FN __host__ __device__ inline
+#else
+#define POLAR_PLAN_FN inline
+#endif
+POLAR_PLAN_FN long long cell_bin(long long c, long long ncell, bool inert, bool split) { return (split && inert) ? ncell + c : c; }
+// what build_cells sizes by the bins: the count / scan / fill / sort range, the entries of the count table (zeroed), of the
+// fill counters (zeroed; front counters first, the back counters of "polarizable first" from fill_back on) and of the
+// scan's output (nbins + 1 written)
+struct CellBins { long long nbins, cnt, fill, fill_back, first; };
+inline CellBins cell_bins(long long ncell, bool split) {
+  const long long nb = split ? 2 * ncell : ncell;
+  return CellBins{nb, nb + 1, 2 * (nb + 1), nb + 1, nb + 2};
+}
+// cell indices and bin indices are 32-bit on the device
+inline bool cell_bins_fit(long long ncell, bool split) { return cell_bins(ncell, split).nbins < (1ll << 31) - 1; }
+
 // ---- pitches of the row lists (multiples of 64) ---------------------------------------------------------------------------
 // first build: `factor` x the mean sphere population
 inline long long pitch_first(double mean, double factor) { return (((long long)(factor * mean) + 64) / 64 + 1) * 64; }

@@ -63,17 +63,25 @@ void build_cells(polar_handle *h) {
     for (int k = 0; k < 3; k++) { h->tile_all.start[k] = 0; h->tile_all.stride[k] = 1; h->tile_all.count[k] = g.nc[k]; h->tile_all.nc[k] = g.nc[k]; }
   }
   hipStream_t s = h->stream;
-  h->d_cell_id.ensure(n); h->d_cell_cnt.ensure(ncell + 1); h->d_cell_fill.ensure(2 * (ncell + 1));
-  h->d_cell_first.ensure(ncell + 2); h->d_perm.ensure(n + 1); h->d_inv.ensure(n + 1);
-  zero_many(s, {{h->d_cell_cnt.p, (size_t)(ncell + 1) * sizeof(int)}, {h->d_cell_fill.p, 2 * (size_t)(ncell + 1) * sizeof(int)}});
-  k_cell_count<<<nblk(n, 256), 256, 0, s>>>(n, h->d_x.p, g, h->box, h->d_cell_id.p, h->d_cell_cnt.p);
-  launch_scan(ncell, h->d_cell_cnt.p, h->d_cell_first.p, h->d_scan_a, s);
+  // inert sites (no charge, no polarizability) are binned behind the grid, into a second copy of it (cell_bin, polar_plan.hpp):
+  // cell_first[0 .. ncell], all that the candidate walks and the colouring read, spans the other sites alone, and the record
+  // table holds no inert record between two cells.  On exactly when the lists leave the inert sites out (nl_inert).
+  const bool split = h->nl_inert && h->cell_inert;
+  if (!cell_bins_fit(ncell, split)) throw InputError("the list grid has more cells than a 32-bit bin index holds");
+  const CellBins cb = cell_bins(ncell, split);
+  const bool pol_first = h->pol_first || h->sweep_kernel == 4;
+  h->cell_split = split;
+  h->d_cell_id.ensure(n); h->d_cell_cnt.ensure(cb.cnt); h->d_cell_fill.ensure(cb.fill);
+  h->d_cell_first.ensure(cb.first); h->d_perm.ensure(n + 1); h->d_inv.ensure(n + 1);
+  zero_many(s, {{h->d_cell_cnt.p, (size_t)cb.cnt * sizeof(int)}, {h->d_cell_fill.p, (size_t)cb.fill * sizeof(int)}});
+  k_cell_count<<<nblk(n, 256), 256, 0, s>>>(n, h->d_x.p, h->d_q.p, h->d_alpha.p, g, h->box, split ? ncell : 0, h->d_cell_id.p, h->d_cell_cnt.p);
+  launch_scan(cb.nbins, h->d_cell_cnt.p, h->d_cell_first.p, h->d_scan_a, s);
   k_cell_fill<<<nblk(n, 256), 256, 0, s>>>(n, h->d_cell_id.p, h->d_cell_first.p, h->d_cell_fill.p,
-                                           (h->pol_first || h->sweep_kernel == 4) ? h->d_cell_fill.p + ncell + 1 : nullptr, h->d_alpha.p, h->d_perm.p, h->d_inv.p);
+                                           pol_first ? h->d_cell_fill.p + cb.fill_back : nullptr, h->d_alpha.p, h->d_perm.p, h->d_inv.p);
   // the order inside a cell follows the atomics of k_cell_fill: put it into atom order -- always, not only for `deterministic
   // yes` (reproducible sums): the device colouring breaks its ties by position in the cell, and a colouring that changed from
   // run to run would make unconverged (`fixed_iteration`) results differ at 1e-6 instead of the 1e-9 of the in-place race
-  k_cell_sort<<<nblk(ncell, 4), 256, 0, s>>>(ncell, h->d_cell_first.p, (h->pol_first || h->sweep_kernel == 4) ? h->d_cell_fill.p : nullptr, h->d_perm.p, h->d_inv.p);
+  k_cell_sort<<<nblk(cb.nbins, 4), 256, 0, s>>>(cb.nbins, h->d_cell_first.p, pol_first ? h->d_cell_fill.p : nullptr, h->d_perm.p, h->d_inv.p);
   h->sorted = true;
   if (sharded(h)) {
     h->d_ownrows.ensure(own_n(h) + 1);
