@@ -332,6 +332,33 @@ int polar_field_at(polar_handle *h, long long npoints, const double *x /*[npoint
                    const int *molecule, double *e_static, double *e_induced /* [npoints][3] each */,
                    double *phi_static, double *phi_induced /* [npoints] each */, double *device_ms);
 
+/* ---- ... with polar_ewald: the Ewald field and potential at points (extension) ---------------
+ * polar_field_at for a handle with polar_ewald > 0: the static sums are the Ewald ones the dipoles of such
+ * a handle feel, e.g. the electrostatic potential of the periodic framework in a pore.  Arguments, null rules, units, passes
+ * (POLAR_FIELD_AT_CHUNK), wrapping of far points, input checks and the call window are those of polar_field_at.  With d, r,
+ * e2s, rc as there, g = g_ewald, G(r) = 2g/sqrt(pi) e^(-g^2 r^2), B1 = (erfc(gr)/r + G) / r^2, S(k) = sum_j q_j e^{ik.x_j}, the
+ * half space of k-vectors and c_k = (8 pi / V) e^(-k^2/4g^2) / k^2 of the step (|k| <= 2 g sqrt(-ln polar_ewald)), Q = sum_j q_j:
+ *   e_static[3] = e2s [ sum_kept q_j B1 d + sum_excl q_j (B1 - 1/r^3) d + sum_k c_k k Im(e^{ik.p} conj S(k)) ]
+ *   phi_static  = e2s [ sum_kept q_j erfc(gr)/r - sum_excl q_j erf(gr)/r + sum_k c_k Re(e^{ik.p} conj S(k)) - pi Q / (g^2 V) ]
+ *   e_induced, phi_induced: exactly polar_field_at's (polar_ewald leaves the dipole tensor cut at the minimum image / dd_cutoff)
+ * The real-space sums run over the minimum-image atoms with r^2 <= rc^2, as the step's.  An atom is EXCLUDED when the point
+ * carries its (non-zero) molecule id, when it is the point's skip_atom, or when it sits exactly on the point: exclusion takes the
+ * nearest image's 1/r part off and leaves its periodic images in -- the step's own rule.  At r == 0 the erf form takes its
+ * limit: nothing in the field, -q_j 2g/sqrt(pi) in phi_static.  The skip_atom and an atom at r == 0 add nothing to the induced
+ * sums.  The Q term is the neutralising background: with it the potential of a charged box does not depend on g.
+ * -grad phi_static = e_static except across the rc shell, where both jump by O(erfc(g rc)).  With skip_atom = i and the molecule
+ * of atom i, a point on atom i sees what atom i sees: e_static = ef_static[i], alpha_i (e_static + e_induced) = mu[i].
+ * Cost: one phase term per (point, k-vector) -- a 128^3 map of a box with 4.4e4 k-vectors is 9e10 of them; a particle-mesh
+ * sum would be the answer at that size and is not offered.  A point's result depends on the point, the records and the
+ * k-vector table alone: not on its pass, the other points or their order.  The handle is not disturbed.
+ * POLAR_ERR_UNSUPPORTED with polar_ewald == 0 (polar_field_at is the call there), on a row-sharded handle and with the lab
+ * build's tile sweep; POLAR_ERR_STATE outside the call window; POLAR_ERR_INPUT as polar_field_at.
+ * polar_pair_extract "ewald_field_at_ms": double[2], device ms of the last call's real-space kernel and of its reciprocal kernels;
+ * "ewald_field_ms": device ms of the field half of the last step's reciprocal work (structure factors and k_ew_field). */
+int polar_ewald_field_at(polar_handle *h, long long npoints, const double *x /*[npoints][3]*/, const int *skip_atom,
+                         const int *molecule, double *e_static, double *e_induced /* [npoints][3] each */,
+                         double *phi_static, double *phi_induced /* [npoints] each */, double *device_ms);
+
 
 /* ---- stepwise / sharded interface (multi-GPU driver: one process per GPU, rows sharded) ------
  * The reference is single-process only (README.md:5; its pack_comm/unpack_comm are dead code,

@@ -140,6 +140,7 @@ EXPORTS = {
     "polar_download": (C.c_int, [C.c_void_p, C.c_char_p, _dp, C.c_longlong]),
     "polar_upload_mu": (C.c_int, [C.c_void_p, _dp, C.c_longlong]),
     "polar_field_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
+    "polar_ewald_field_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "polar_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "polar_set_row_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "polar_set_global_count": (C.c_int, [C.c_void_p, C.c_longlong]),
@@ -490,6 +491,10 @@ class PolarPair:
         index per point that contributes nothing, or -1; ``molecule`` [m]: a molecule id per point whose atoms are left out
         of the static sums, or 0.  Returns a dict: e_static, e_induced [m, 3], phi_static, phi_induced [m] (None without
         ``potential``), ms (device time of the kernels)."""
+        return self._field_at(self.L.polar_field_at, x, skip_atom, molecule, potential)
+
+    def _field_at(self, entry, x, skip_atom, molecule, potential):
+        """the call behind ``field_at`` and ``ewald_field_at``: the two entry points take the same arguments"""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
         m = len(x)
         sk = None if skip_atom is None else np.ascontiguousarray(skip_atom, dtype=np.int32)
@@ -498,10 +503,20 @@ class PolarPair:
         es, ei = np.zeros((m, 3)), np.zeros((m, 3))
         ps, pi = (np.zeros(m), np.zeros(m)) if potential else (None, None)
         ms = C.c_double()
-        self._ck(self.L.polar_field_at(self.h, m, _dptr(x), None if sk is None else _iptr(sk), None if mo is None else _iptr(mo),
-                                       _dptr(es), _dptr(ei), None if ps is None else _dptr(ps), None if pi is None else _dptr(pi),
-                                       C.byref(ms)))
+        self._ck(entry(self.h, m, _dptr(x), None if sk is None else _iptr(sk), None if mo is None else _iptr(mo),
+                       _dptr(es), _dptr(ei), None if ps is None else _dptr(ps), None if pi is None else _dptr(pi), C.byref(ms)))
         return dict(e_static=es, e_induced=ei, phi_static=ps, phi_induced=pi, ms=ms.value)
+
+    def ewald_field_at(self, x, skip_atom=None, molecule=None, potential=True):
+        """``field_at`` for a handle with ``polar_ewald``: the static sums are the Ewald ones (polar_ewald_field_at in
+        include/polar_mi355x.h).  The same arguments and the same dict, plus ms_real and ms_recip: the device time of the
+        real-space kernel and of the reciprocal kernels."""
+        out = self._field_at(self.L.polar_ewald_field_at, x, skip_atom, molecule, potential)
+        dim = C.c_int()
+        ptr = self.L.polar_pair_extract(self.h, b"ewald_field_at_ms", C.byref(dim))
+        t = C.cast(C.c_void_p(ptr), _dp)
+        out.update(ms_real=t[0], ms_recip=t[1])
+        return out
 
     def grid_points(self, shape):
         """The points of ``field_grid``: cell-centred fractional coordinates ((i + 1/2) / nx, (j + 1/2) / ny, (k + 1/2) / nz) of
@@ -517,7 +532,15 @@ class PolarPair:
         """``field_at`` on an (nx, ny, nz) grid of cell-centred points of the handle's box (``grid_points``).  x runs fastest,
         so consecutive points are neighbours; the arrays come back as (nz, ny, nx[, 3])."""
         nx, ny, nz = (int(v) for v in shape)
-        out = self.field_at(self.grid_points((nx, ny, nz)), potential=potential)
+        return self._grid_shaped(self.field_at(self.grid_points((nx, ny, nz)), potential=potential), nx, ny, nz)
+
+    def ewald_field_grid(self, shape, potential=True):
+        """``ewald_field_at`` on the grid of ``field_grid``: the same points, the same shapes."""
+        nx, ny, nz = (int(v) for v in shape)
+        return self._grid_shaped(self.ewald_field_at(self.grid_points((nx, ny, nz)), potential=potential), nx, ny, nz)
+
+    @staticmethod
+    def _grid_shaped(out, nx, ny, nz):
         for k in ("e_static", "e_induced"):
             out[k] = out[k].reshape(nz, ny, nx, 3)
         for k in ("phi_static", "phi_induced"):

@@ -333,6 +333,10 @@ const void *polar_pair_extract(const polar_handle *h, const char *name, int *dim
     if (guarded(m, [&]() { inert_counters(m); return POLAR_OK; }) != POLAR_OK) return nullptr;
     return name[0] == 'n' ? &h->nl_entries : &h->force_rows;
   }
+  // device time of the last polar_ewald_field_at call: [0] the real-space kernel, [1] the reciprocal kernels and the fold
+  if (strcmp(name, "ewald_field_at_ms") == 0) { if (dim) *dim = 1; return h->ew_fa_ms; }
+  // device time of the last polar_ewald step's field half (structure factors and k_ew_field), the part of ms_kspace before the solve
+  if (strcmp(name, "ewald_field_ms") == 0) { if (dim) *dim = 0; return &h->ew_field_ms; }   // (a scalar, as "cut_coul")
   if (dim) *dim = 2;
   if (strcmp(name, "epsilon") == 0) return h->ph.epsilon.data();
   if (strcmp(name, "sigma") == 0) return h->ph.sigma.data();
@@ -773,6 +777,35 @@ int polar_field_at(polar_handle *h, long long npoints, const double *x, const in
       field_at_pass(h, m, x + 3 * p0, skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr,
                     e_static ? e_static + 3 * p0 : nullptr, e_induced ? e_induced + 3 * p0 : nullptr,
                     phi_static ? phi_static + p0 : nullptr, phi_induced ? phi_induced + p0 : nullptr, device_ms);
+    }
+    return (int)POLAR_OK;
+  });
+}
+
+/* ---- ... and with polar_ewald: the Ewald field and potential (polar_ewald_field_at.hpp) -------- */
+int polar_ewald_field_at(polar_handle *h, long long npoints, const double *x, const int *skip_atom, const int *molecule,
+                         double *e_static, double *e_induced, double *phi_static, double *phi_induced, double *device_ms) {
+  return guarded(h, [&]() {
+    need_device(h);
+    if (!ewald_on(h)) throw Unsupported("polar_ewald_field_at: the handle runs without polar_ewald; polar_field_at maps its shifted-force field");
+    if (sharded(h)) throw Unsupported("polar_ewald_field_at: not offered on a row-sharded handle");
+    if (tile_mode(h)) throw Unsupported("polar_ewald_field_at: not offered with the tile sweep (lab build)");
+    if (!h->field_ready) throw std::runtime_error("polar_ewald_field_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
+    if (npoints < 0) throw InputError("polar_ewald_field_at: negative point count");
+    if (device_ms) *device_ms = 0.0;
+    h->ew_fa_ms[0] = h->ew_fa_ms[1] = 0.0;
+    if (npoints == 0) return (int)POLAR_OK;
+    if (!x) throw InputError("polar_ewald_field_at: null pointer");
+    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
+    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    HIPCHECK(hipSetDevice(h->device));
+    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
+    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
+    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
+      const int m = (int)std::min(chunk, npoints - p0);
+      ewald_field_at_pass(h, m, x + 3 * p0, skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr,
+                          e_static ? e_static + 3 * p0 : nullptr, e_induced ? e_induced + 3 * p0 : nullptr,
+                          phi_static ? phi_static + p0 : nullptr, phi_induced ? phi_induced + p0 : nullptr, device_ms);
     }
     return (int)POLAR_OK;
   });

@@ -318,6 +318,15 @@ struct polar_handle {
   DBuf<double> d_fa_x, d_fa_out;
   DBuf<int> d_fa_idx;
   Event ev_fa[2];
+  // polar_ewald_field_at (polar_ewald_field_at.hpp): the chunk partials of the reciprocal sums of a pass (freed with the pass
+  // buffers), Q = the sum of the charges (summed once per call window: ew_q_valid is cleared where a step begins), the event
+  // behind the reciprocal kernels, and the device time of the last call's real-space / reciprocal kernels
+  // (polar_pair_extract "ewald_field_at_ms")
+  DBuf<double> d_fa_part, d_fa_q;
+  bool ew_q_valid = false;
+  Event ev_fa_k;
+  double ew_fa_ms[2] = {0.0, 0.0};
+  double ew_field_ms = 0.0;   // device time of the last step's ewald_field (S(k) and k_ew_field): polar_pair_extract "ewald_field_ms"
   // Everything above frees itself.  What is left to do first: let the device finish with it.
   ~polar_handle() {
     if (!device_set) return;
@@ -517,6 +526,9 @@ void build_cluster_lists(polar_handle *h);
 // time added to *ms; synchronous on return
 void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
                    double *e_induced, double *phi_static, double *phi_induced, double *ms);
+// the same for polar_ewald_field_at: real-space and induced sums, then the reciprocal sums of the step's k-vectors
+void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
+                         double *e_induced, double *phi_static, double *phi_induced, double *ms);
 // ---- polar_color.hip --------------------------------------------------------------------------------------------------
 void ensure_colors(polar_handle *h);
 struct ColorComm {   // what a distributed colouring needs from the transport (polar_dist.hip)

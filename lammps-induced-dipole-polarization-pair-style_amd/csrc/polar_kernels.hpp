@@ -23,7 +23,9 @@
 // polar_lists.hpp (list mode: cells, neighbor lists, exchange), polar_tiles.hpp (list mode: the tile sweep
 // -- one workgroup per cell, neighbour records staged in LDS -- and its builder), polar_ewald.hpp (`polar_ewald`: the
 // reciprocal-space static field and charge-dipole forces); and polar_field_at.hpp (`polar_field_at`: field and potential of the
-// polarized box at arbitrary points, one wave per point; its pair arithmetic in the plain-C++ polar_point_pair.hpp).
+// polarized box at arbitrary points, one wave per point; its pair arithmetic in the plain-C++ polar_point_pair.hpp) with
+// polar_ewald_field_at.hpp (`polar_ewald_field_at`: the same map for `polar_ewald` handles, real-space and reciprocal sums;
+// arithmetic in the plain-C++ polar_ewald_point.hpp).
 #pragma once
 
 #include "polar_common.hpp"
@@ -35,3 +37,4 @@
 #include "polar_tiles.hpp"
 #include "polar_ewald.hpp"
 #include "polar_field_at.hpp"   // the field and the potential of the polarized box at arbitrary points (polar_field_at)
+#include "polar_ewald_field_at.hpp"   // ... with `polar_ewald`: the Ewald field and potential (polar_ewald_field_at)

@@ -728,6 +728,7 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
   need_device(h);
   h->field_ready = false;   // (polar_field_at: the records are being rewritten until the step has finished)
   h->d_fa_x.release(); h->d_fa_idx.release(); h->d_fa_out.release();   // a probe's pass buffers (100 bytes per point) do not outlive the step it looked at
+  h->d_fa_part.release(); h->ew_q_valid = false;   // (polar_ewald_field_at: its chunk partials; the charges may be other ones)
   if (!h->types_set || !h->coul_set) throw std::runtime_error("polar_compute before the pair tables were set: polar_pair_init (or polar_set_types), then polar_set_coul with the Coulomb tables of Pair::init_tables unless pair_modify table 0");
   if (!h->box_set || !h->atoms_set || !h->neigh_set) throw std::runtime_error("polar_compute before polar_set_box/polar_set_atoms/polar_set_neighbors");
   const polar_settings &st = h->ph.st;
@@ -1033,6 +1034,7 @@ int phase_finish(polar_handle *h, polar_result *out) {
     HIPCHECK(hipEventElapsedTime(&a, h->ev_ks[0], h->ev_ks[1]));
     HIPCHECK(hipEventElapsedTime(&b, h->ev_ks[2], h->ev_ks[3]));
     out->ms_kspace = (double)a + (double)b;
+    h->ew_field_ms = (double)a;   // (polar_pair_extract "ewald_field_ms": the field half alone, the yardstick of tools/ewald_field_at_cost.py)
     out->nkvec = h->ew_nk;
   }
   long long rb = (long long)sc.rmin_bits;
@@ -1199,4 +1201,82 @@ void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom
   float t = 0.f;
   HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
   if (ms) *ms += (double)t;
+}
+
+// polar_ewald_field_at, one pass: k_ew_point_real (polar_ewald_field_at.hpp) writes the real-space static sums and the induced
+// sums of the m points; then, for runs of points sized so that the chunk partials stay within 64 MB, k_ew_point_recip over
+// (points, row chunks of the step's k-vector table) and k_ew_point_fold.  S(k) in d_ew_s is the finished step's: nothing writes
+// it after ewald_field.  Nothing of the handle's step state is written.
+void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
+                         double *e_induced, double *phi_static, double *phi_induced, double *ms) {
+  const polar_settings &st = h->ph.st;
+  const bool ap = !(st.dd_cutoff > 0.0);
+  const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
+  const bool phi = phi_static || phi_induced;
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fa_out.ensure(8 * mm);
+  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
+  if (!h->ev_fa_k.e) h->ev_fa_k.create();
+  HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
+  int *d_skip = nullptr, *d_pmol = nullptr;
+  if (skip_atom) { d_skip = h->d_fa_idx.p; HIPCHECK(hipMemcpyAsync(d_skip, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  if (molecule) { d_pmol = h->d_fa_idx.p + mm; HIPCHECK(hipMemcpyAsync(d_pmol, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  const double rc = st.cut_coul, g = h->P.g_ewald;
+  const PointCut cut{rc * rc, st.dd_cutoff * st.dd_cutoff, 1.0 / (rc * rc), 2.0 / rc, st.polar_damp};
+  const EwPointParm ewp = make_ew_point_parm(g);
+  const FieldAtOut out{h->d_fa_out.p};
+  const double e2s = std::sqrt(h->P.qqrd2e);
+  const ExpCoef K = make_expcoef();
+  CellGrid cg = h->grid;   // (exact mode has built no grid: the kernels take the box origin from it in both modes)
+  for (int k = 0; k < 3; k++) cg.lo[k] = h->boxlo[k];
+  if (!h->ew_q_valid) {   // Q of the neutralising-background term, once per call window
+    h->d_fa_q.ensure(1);
+    k_ew_point_qsum<<<1, 256, 0, s>>>(h->nlocal, h->d_rec0.p, h->d_fa_q.p);
+    HIPCHECK(hipGetLastError());   // (a launch that failed leaves no Q marked valid)
+    h->ew_q_valid = true;
+  }
+  const dim3 grid(nblk(m, POLAR_ROWS_PER_BLOCK)), block(POLAR_BLOCK);
+  HIPCHECK(hipEventRecord(h->ev_fa[0], s));
+#define FA(AP, D, P)                                                                                                               \
+  k_ew_point_real<AP, D, P><<<grid, block, 0, s>>>(m, h->d_fa_x.p, d_skip, d_pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,    \
+                                                   h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, cg,                \
+                                                   AP ? nullptr : h->d_cell_first.p, cut, ewp, e2s, K, out)
+#define FAP(AP, D) do { if (phi) FA(AP, D, true); else FA(AP, D, false); } while (0)
+  if (ap) { if (expd) FAP(true, 0); else FAP(true, 1); }
+  else    { if (expd) FAP(false, 0); else FAP(false, 1); }
+#undef FAP
+#undef FA
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa[1], s));
+  // reciprocal space
+  const int nk = h->ew_nk, nrow = nk > 0 ? h->ew_nrow : 0;
+  const int nchunk = ew_point_chunks(nrow, nk), rpc = ew_point_rows_per_chunk(nrow, nk);
+  const double vol = h->box.prd[0] * h->box.prd[1] * h->box.prd[2];
+  const double qterm = -3.14159265358979323846 / (g * g * vol);
+  const size_t per_point = (size_t)std::max(nchunk, 1) * 4 * sizeof(double);
+  const int run = (int)std::max<size_t>(256, std::min<size_t>(mm, ((size_t)64 << 20) / per_point / 256 * 256));
+  h->d_fa_part.ensure((size_t)std::max(nchunk, 1) * 4 * std::min<size_t>(mm, (size_t)run));
+  for (int p0 = 0; p0 < m; p0 += run) {
+    const int np = std::min(run, m - p0);
+    if (nchunk > 0) {
+      const dim3 gk(nblk(np, 256), nchunk);
+      if (phi) k_ew_point_recip<true><<<gk, 256, 0, s>>>(np, p0, h->d_fa_x.p, h->box, cg.lo[0], cg.lo[1], cg.lo[2], ew_cell(h), nrow, rpc, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_fa_part.p);
+      else     k_ew_point_recip<false><<<gk, 256, 0, s>>>(np, p0, h->d_fa_x.p, h->box, cg.lo[0], cg.lo[1], cg.lo[2], ew_cell(h), nrow, rpc, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_fa_part.p);
+    }
+    if (phi) k_ew_point_fold<true><<<nblk(np, 256), 256, 0, s>>>(np, p0, m, nchunk, h->d_fa_part.p, e2s, qterm, h->d_fa_q.p, out);
+    else     k_ew_point_fold<false><<<nblk(np, 256), 256, 0, s>>>(np, p0, m, nchunk, h->d_fa_part.p, e2s, qterm, h->d_fa_q.p, out);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa_k, s));
+  if (e_static) HIPCHECK(hipMemcpyAsync(e_static, out.es(), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (e_induced) HIPCHECK(hipMemcpyAsync(e_induced, out.ei(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (phi_static) HIPCHECK(hipMemcpyAsync(phi_static, out.ps(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (phi_induced) HIPCHECK(hipMemcpyAsync(phi_induced, out.pi(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  float t = 0.f, tk = 0.f;
+  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
+  HIPCHECK(hipEventElapsedTime(&tk, h->ev_fa[1], h->ev_fa_k));
+  h->ew_fa_ms[0] += (double)t; h->ew_fa_ms[1] += (double)tk;
+  if (ms) *ms += (double)t + (double)tk;
 }
