@@ -811,6 +811,34 @@ int polar_ewald_field_at(polar_handle *h, long long npoints, const double *x, co
   });
 }
 
+/* ---- ... on a regular grid of the cell: the reciprocal sums as three 1-D transforms (polar_ewald_field_grid.hpp) -------- */
+int polar_ewald_field_grid(polar_handle *h, const int n[3], const double offset[3], double *x_out, double *e_static, double *e_induced,
+                           double *phi_static, double *phi_induced, double *device_ms) {
+  return guarded(h, [&]() {
+    need_device(h);
+    if (!ewald_on(h)) throw Unsupported("polar_ewald_field_grid: the handle runs without polar_ewald; polar_field_at maps its shifted-force field");
+    if (sharded(h)) throw Unsupported("polar_ewald_field_grid: not offered on a row-sharded handle");
+    if (tile_mode(h)) throw Unsupported("polar_ewald_field_grid: not offered with the tile sweep (lab build)");
+    if (!h->field_ready) throw std::runtime_error("polar_ewald_field_grid: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
+    double off[3];
+    const long long npoints = check_grid(n, offset, off);
+    if (device_ms) *device_ms = 0.0;
+    h->ew_fa_ms[0] = h->ew_fa_ms[1] = 0.0;
+    HIPCHECK(hipSetDevice(h->device));
+    EwGridCall call;
+    ewald_field_grid_begin(h, n, off, call, device_ms);
+    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
+    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
+    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
+      const int m = (int)std::min(chunk, npoints - p0);
+      ewald_field_grid_pass(h, call, p0, m, x_out ? x_out + 3 * p0 : nullptr, e_static ? e_static + 3 * p0 : nullptr,
+                            e_induced ? e_induced + 3 * p0 : nullptr, phi_static ? phi_static + p0 : nullptr,
+                            phi_induced ? phi_induced + p0 : nullptr, device_ms);
+    }
+    return (int)POLAR_OK;
+  });
+}
+
 /* ---- stepwise / sharded interface (multi-GPU driver, parallel.py) --------------------------- */
 int polar_set_stream(polar_handle *h, void *hip_stream) {
   return guarded(h, [&]() {

@@ -326,6 +326,10 @@ struct polar_handle {
   bool ew_q_valid = false;
   Event ev_fa_k;
   double ew_fa_ms[2] = {0.0, 0.0};
+  // polar_ewald_field_grid (polar_ewald_field_grid.hpp): the phase tables and T of a call, V of a run of lines (at most 64 MB),
+  // the first row of every h (freed with the pass buffers)
+  DBuf<double2> d_eg_tab, d_eg_t, d_eg_v;
+  DBuf<int> d_eg_first;
   double ew_field_ms = 0.0;   // device time of the last step's ewald_field (S(k) and k_ew_field): polar_pair_extract "ewald_field_ms"
   // Everything above frees itself.  What is left to do first: let the device finish with it.
   ~polar_handle() {
@@ -529,6 +533,19 @@ void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom
 // the same for polar_ewald_field_at: real-space and induced sums, then the reciprocal sums of the step's k-vectors
 void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
                          double *e_induced, double *phi_static, double *phi_induced, double *ms);
+// polar_ewald_field_grid: what the passes of a call share -- the grid, the layout of the tables and of the scratch
+// (polar_plan.hpp) and the lines of V per run.  ewald_field_grid_begin fills it, builds the phase tables and runs stage 1 on
+// the device (their time goes to the reciprocal share); ewald_field_grid_pass handles the points [p0, p0 + m) of the flat order:
+// points, real-space and induced sums, stages 2 and 3 per run of whole lines; x_out (may be null) gets the pass's points.
+struct EwGridCall {
+  EwGrid g;
+  EwGridPlan plan;
+  EwGridSizes sz;
+  long long lines_per_run = 1;
+};
+void ewald_field_grid_begin(polar_handle *h, const int n[3], const double off[3], EwGridCall &c, double *ms);
+void ewald_field_grid_pass(polar_handle *h, const EwGridCall &c, long long p0, int m, double *x_out, double *e_static, double *e_induced,
+                           double *phi_static, double *phi_induced, double *ms);
 // ---- polar_color.hip --------------------------------------------------------------------------------------------------
 void ensure_colors(polar_handle *h);
 struct ColorComm {   // what a distributed colouring needs from the transport (polar_dist.hip)

@@ -69,6 +69,24 @@ inline void check_points(long long npoints, const double *x, const int *skip_ato
 // pass's buffers (100 bytes per point) stay below 2 GB
 inline long long field_at_chunk(long long env) { return env <= 0 ? (1ll << 20) : std::min(env, 1ll << 24); }
 
+// ---- polar_ewald_field_grid -------------------------------------------------------------------------------------------------
+// The grid of a call: every n[a] >= 1, n[0] n[1] n[2] <= 2^31 - 1 (a flat index is an int), every offset finite and in [0, 1)
+// (offset null: the cell centres, 0.5 each).  Returns the number of points and fills off.
+inline long long check_grid(const int n[3], const double *offset, double off[3]) {
+  if (!n) throw InputError("polar_ewald_field_grid: null pointer");
+  long long npts = 1;
+  for (int a = 0; a < 3; a++) {
+    if (n[a] < 1) throw InputError("polar_ewald_field_grid: a grid count below 1");
+    npts *= n[a];   // (at most 2^31 - 1 times a value checked to be at most 2^31 - 1: no overflow of 64 bits)
+    if (npts > 2147483647LL) throw InputError("polar_ewald_field_grid: more than 2^31 - 1 grid points");
+  }
+  for (int a = 0; a < 3; a++) {
+    off[a] = offset ? offset[a] : 0.5;
+    if (!(off[a] >= 0.0 && off[a] < 1.0)) throw InputError("polar_ewald_field_grid: offset outside [0, 1)");
+  }
+  return npts;
+}
+
 // ---- pair tables ----------------------------------------------------------------------------------------------------------
 // The LJ tables repacked so that the half-list loop reads one 64-byte line per type pair:
 // t = lj1, lj2, lj3, lj4, offset, cut_ljsq, cutsq  ->  cutsq, cut_ljsq, lj1, lj2, lj3, lj4, offset, pad.

@@ -25,7 +25,8 @@
 // reciprocal-space static field and charge-dipole forces); and polar_field_at.hpp (`polar_field_at`: field and potential of the
 // polarized box at arbitrary points, one wave per point; its pair arithmetic in the plain-C++ polar_point_pair.hpp) with
 // polar_ewald_field_at.hpp (`polar_ewald_field_at`: the same map for `polar_ewald` handles, real-space and reciprocal sums;
-// arithmetic in the plain-C++ polar_ewald_point.hpp).
+// arithmetic in the plain-C++ polar_ewald_point.hpp) and polar_ewald_field_grid.hpp (`polar_ewald_field_grid`: that map on a
+// regular grid of the cell, the reciprocal sums as three 1-D transforms; arithmetic in the plain-C++ polar_ewald_grid.hpp).
 #pragma once
 
 #include "polar_common.hpp"
@@ -38,3 +39,4 @@
 #include "polar_ewald.hpp"
 #include "polar_field_at.hpp"   // the field and the potential of the polarized box at arbitrary points (polar_field_at)
 #include "polar_ewald_field_at.hpp"   // ... with `polar_ewald`: the Ewald field and potential (polar_ewald_field_at)
+#include "polar_ewald_field_grid.hpp" // ... on a regular grid of the cell (polar_ewald_field_grid)

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
+#include <cstdlib>
 #include <vector>
 
 namespace polar {
@@ -180,6 +181,61 @@ inline SfacChunks ewald_sfac_chunks(int n, int nk, int tile) {
   c.chunk = std::max(1, nblk(std::max(n, 1), c.nchunk));
   c.nchunk = nblk(std::max(n, 1), c.chunk);
   return c;
+}
+
+// ---- polar_ewald_field_grid: the layout of a call, from the k-vector table alone (polar_ewald_grid.hpp) ------------------------
+// Index bounds of the rows table (rows[r] = {h, k, first l, first index}, rows[nrow].w = nk): hmax, kmax = max |k|,
+// lmax = max |l| over the rows' runs of l; first[h] = the first row of h, first[hmax + 1] = nrow (the table is in (h, k) order:
+// the rows of an h are one run -- `ok` says that this table's are, and that h starts at 0 and skips no value).
+struct EwGridPlan {
+  int hmax = 0, kmax = 0, lmax = 0;
+  std::vector<int> first;
+  bool ok = true;
+};
+inline EwGridPlan ew_grid_plan(const PlanI4 *rows, int nrow) {
+  EwGridPlan p;
+  for (int r = 0; r < nrow; r++) {
+    const int l0 = rows[r].z, l1 = l0 + (rows[r + 1].w - rows[r].w) - 1;
+    p.hmax = std::max(p.hmax, rows[r].x);
+    p.kmax = std::max(p.kmax, std::abs(rows[r].y));
+    p.lmax = std::max(p.lmax, std::max(std::abs(l0), std::abs(l1)));
+    if (rows[r].x < 0 || l1 < l0 || (r > 0 && rows[r].x < rows[r - 1].x)) p.ok = false;
+  }
+  p.first.assign((size_t)p.hmax + 2, nrow);
+  for (int r = nrow - 1; r >= 0; r--)
+    if (rows[r].x >= 0 && rows[r].x <= p.hmax) p.first[(size_t)rows[r].x] = r;
+  for (int h = p.hmax - 1; h >= 0; h--)   // (an h without rows -- no table of ewald_kvectors has one -- starts where the next one does)
+    if (p.first[(size_t)h] > p.first[(size_t)h + 1]) p.first[(size_t)h] = p.first[(size_t)h + 1];
+  if (nrow > 0 && p.first[0] != 0) p.ok = false;
+  return p;
+}
+// Table and scratch sizes of a call on an (nx, ny, nz) grid, in entries of 16 bytes (one complex number): the three phase
+// tables in one array (x at 0, y at off_y, z at off_z, `tab` in all), T[nrow][nz][4], and the bytes of V per line,
+// (hmax + 1) x 4 sets.
+struct EwGridSizes { size_t off_y, off_z, tab, t, v_line_bytes; };
+inline EwGridSizes ew_grid_sizes(const EwGridPlan &p, int nrow, const int n[3]) {
+  EwGridSizes s;
+  s.off_y = (size_t)(p.hmax + 1) * (size_t)n[0];
+  s.off_z = s.off_y + (size_t)(2 * p.kmax + 1) * (size_t)n[1];
+  s.tab = s.off_z + (size_t)(2 * p.lmax + 1) * (size_t)n[2];
+  s.t = (size_t)nrow * (size_t)n[2] * 4;
+  s.v_line_bytes = (size_t)(p.hmax + 1) * 4 * 16;
+  return s;
+}
+// whole lines of the grid whose V fits the 64 MB that the per-point path spends on its chunk partials (at least one)
+inline long long ew_grid_lines_per_run(size_t v_line_bytes) { return std::max<long long>(1, (long long)(((size_t)64 << 20) / std::max<size_t>(v_line_bytes, 1))); }
+// A pass holds the points [p0, p0 + m) of the flat order and may start and end inside a line of nx points.  Its line
+// sub-ranges: run r computes V of the lines [la, lb) and stage 3 takes the pass's points [q0, q1) of them.
+struct EwGridRun { long long la, lb, q0, q1; };
+inline std::vector<EwGridRun> ew_grid_runs(long long p0, long long m, long long nx, long long lines_per_run) {
+  std::vector<EwGridRun> runs;
+  if (m <= 0 || nx <= 0) return runs;
+  const long long first = p0 / nx, last = (p0 + m - 1) / nx, lpr = std::max<long long>(1, lines_per_run);
+  for (long long la = first; la <= last; la += lpr) {
+    const long long lb = std::min(la + lpr, last + 1);
+    runs.push_back(EwGridRun{la, lb, std::max(p0, la * nx), std::min(p0 + m, lb * nx)});
+  }
+  return runs;
 }
 
 // ---- exact-order Gauss-Seidel on the HBM-resident tensor (polar_exact.hpp) --------------------------------------------------

@@ -729,6 +729,7 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
   h->field_ready = false;   // (polar_field_at: the records are being rewritten until the step has finished)
   h->d_fa_x.release(); h->d_fa_idx.release(); h->d_fa_out.release();   // a probe's pass buffers (100 bytes per point) do not outlive the step it looked at
   h->d_fa_part.release(); h->ew_q_valid = false;   // (polar_ewald_field_at: its chunk partials; the charges may be other ones)
+  h->d_eg_tab.release(); h->d_eg_t.release(); h->d_eg_v.release(); h->d_eg_first.release();   // (polar_ewald_field_grid: tables, T, V)
   if (!h->types_set || !h->coul_set) throw std::runtime_error("polar_compute before the pair tables were set: polar_pair_init (or polar_set_types), then polar_set_coul with the Coulomb tables of Pair::init_tables unless pair_modify table 0");
   if (!h->box_set || !h->atoms_set || !h->neigh_set) throw std::runtime_error("polar_compute before polar_set_box/polar_set_atoms/polar_set_neighbors");
   const polar_settings &st = h->ph.st;
@@ -1203,25 +1204,13 @@ void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom
   if (ms) *ms += (double)t;
 }
 
-// polar_ewald_field_at, one pass: k_ew_point_real (polar_ewald_field_at.hpp) writes the real-space static sums and the induced
-// sums of the m points; then, for runs of points sized so that the chunk partials stay within 64 MB, k_ew_point_recip over
-// (points, row chunks of the step's k-vector table) and k_ew_point_fold.  S(k) in d_ew_s is the finished step's: nothing writes
-// it after ewald_field.  Nothing of the handle's step state is written.
-void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
-                         double *e_induced, double *phi_static, double *phi_induced, double *ms) {
+// The launch of k_ew_point_real (polar_ewald_field_at.hpp) on the m points in d_fa_x, between the events ev_fa[0] and ev_fa[1],
+// behind Q of the neutralising-background term (once per call window): what polar_ewald_field_at and polar_ewald_field_grid share.
+static void ew_point_real_launch(polar_handle *h, int m, const int *d_skip, const int *d_pmol, bool phi) {
   const polar_settings &st = h->ph.st;
   const bool ap = !(st.dd_cutoff > 0.0);
   const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
-  const bool phi = phi_static || phi_induced;
   hipStream_t s = h->stream;
-  const size_t mm = (size_t)m;
-  h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fa_out.ensure(8 * mm);
-  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
-  if (!h->ev_fa_k.e) h->ev_fa_k.create();
-  HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
-  int *d_skip = nullptr, *d_pmol = nullptr;
-  if (skip_atom) { d_skip = h->d_fa_idx.p; HIPCHECK(hipMemcpyAsync(d_skip, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
-  if (molecule) { d_pmol = h->d_fa_idx.p + mm; HIPCHECK(hipMemcpyAsync(d_pmol, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
   const double rc = st.cut_coul, g = h->P.g_ewald;
   const PointCut cut{rc * rc, st.dd_cutoff * st.dd_cutoff, 1.0 / (rc * rc), 2.0 / rc, st.polar_damp};
   const EwPointParm ewp = make_ew_point_parm(g);
@@ -1249,6 +1238,28 @@ void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *ski
 #undef FA
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa[1], s));
+}
+
+// polar_ewald_field_at, one pass: k_ew_point_real (polar_ewald_field_at.hpp) writes the real-space static sums and the induced
+// sums of the m points; then, for runs of points sized so that the chunk partials stay within 64 MB, k_ew_point_recip over
+// (points, row chunks of the step's k-vector table) and k_ew_point_fold.  S(k) in d_ew_s is the finished step's: nothing writes
+// it after ewald_field.  Nothing of the handle's step state is written.
+void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
+                         double *e_induced, double *phi_static, double *phi_induced, double *ms) {
+  const bool phi = phi_static || phi_induced;
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fa_out.ensure(8 * mm);
+  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
+  if (!h->ev_fa_k.e) h->ev_fa_k.create();
+  HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
+  int *d_skip = nullptr, *d_pmol = nullptr;
+  if (skip_atom) { d_skip = h->d_fa_idx.p; HIPCHECK(hipMemcpyAsync(d_skip, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  if (molecule) { d_pmol = h->d_fa_idx.p + mm; HIPCHECK(hipMemcpyAsync(d_pmol, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  ew_point_real_launch(h, m, d_skip, d_pmol, phi);
+  const double g = h->P.g_ewald, e2s = std::sqrt(h->P.qqrd2e);
+  const FieldAtOut out{h->d_fa_out.p};
+  const double *lo = h->boxlo;
   // reciprocal space
   const int nk = h->ew_nk, nrow = nk > 0 ? h->ew_nrow : 0;
   const int nchunk = ew_point_chunks(nrow, nk), rpc = ew_point_rows_per_chunk(nrow, nk);
@@ -1261,14 +1272,100 @@ void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *ski
     const int np = std::min(run, m - p0);
     if (nchunk > 0) {
       const dim3 gk(nblk(np, 256), nchunk);
-      if (phi) k_ew_point_recip<true><<<gk, 256, 0, s>>>(np, p0, h->d_fa_x.p, h->box, cg.lo[0], cg.lo[1], cg.lo[2], ew_cell(h), nrow, rpc, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_fa_part.p);
-      else     k_ew_point_recip<false><<<gk, 256, 0, s>>>(np, p0, h->d_fa_x.p, h->box, cg.lo[0], cg.lo[1], cg.lo[2], ew_cell(h), nrow, rpc, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_fa_part.p);
+      if (phi) k_ew_point_recip<true><<<gk, 256, 0, s>>>(np, p0, h->d_fa_x.p, h->box, lo[0], lo[1], lo[2], ew_cell(h), nrow, rpc, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_fa_part.p);
+      else     k_ew_point_recip<false><<<gk, 256, 0, s>>>(np, p0, h->d_fa_x.p, h->box, lo[0], lo[1], lo[2], ew_cell(h), nrow, rpc, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_fa_part.p);
     }
     if (phi) k_ew_point_fold<true><<<nblk(np, 256), 256, 0, s>>>(np, p0, m, nchunk, h->d_fa_part.p, e2s, qterm, h->d_fa_q.p, out);
     else     k_ew_point_fold<false><<<nblk(np, 256), 256, 0, s>>>(np, p0, m, nchunk, h->d_fa_part.p, e2s, qterm, h->d_fa_q.p, out);
   }
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa_k, s));
+  if (e_static) HIPCHECK(hipMemcpyAsync(e_static, out.es(), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (e_induced) HIPCHECK(hipMemcpyAsync(e_induced, out.ei(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (phi_static) HIPCHECK(hipMemcpyAsync(phi_static, out.ps(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (phi_induced) HIPCHECK(hipMemcpyAsync(phi_induced, out.pi(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  float t = 0.f, tk = 0.f;
+  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
+  HIPCHECK(hipEventElapsedTime(&tk, h->ev_fa[1], h->ev_fa_k));
+  h->ew_fa_ms[0] += (double)t; h->ew_fa_ms[1] += (double)tk;
+  if (ms) *ms += (double)t + (double)tk;
+}
+
+// polar_ewald_field_grid, once per call: the layout from the k-vector table (its rows come back from the device: 16 bytes per
+// (h, k) row), then the phase tables (k_ew_grid_tab) and stage 1 (k_ew_grid_l) of polar_ewald_field_grid.hpp.  Their device
+// time is reciprocal time.
+void ewald_field_grid_begin(polar_handle *h, const int n[3], const double off[3], EwGridCall &c, double *ms) {
+  hipStream_t s = h->stream;
+  const int nk = h->ew_nk, nrow = nk > 0 ? h->ew_nrow : 0;
+  std::vector<PlanI4> rows((size_t)nrow + 1, PlanI4{0, 0, 0, 0});
+  if (nrow > 0) {
+    HIPCHECK(hipMemcpyAsync(rows.data(), h->d_ew_rows.p, rows.size() * sizeof(int4), hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+  }
+  c.plan = ew_grid_plan(rows.data(), nrow);
+  if (!c.plan.ok) throw std::runtime_error("polar_ewald_field_grid: the k-vector table is not in (h, k) order");
+  EwGrid &g = c.g;
+  for (int a = 0; a < 3; a++) { g.n[a] = n[a]; g.off[a] = off[a]; g.lo[a] = h->boxlo[a]; }
+  g.ax = h->box.prd[0]; g.bx = h->box.xy; g.by = h->box.prd[1]; g.cx = h->box.xz; g.cy = h->box.yz; g.cz = h->box.prd[2];
+  ew_grid_slo(h->ew_cell, h->boxlo, g.slo);
+  c.sz = ew_grid_sizes(c.plan, nrow, n);
+  c.lines_per_run = ew_grid_lines_per_run(c.sz.v_line_bytes);
+  const int nzb = nblk(n[2], 64);
+  if ((long long)nrow * nzb > 2147483647LL || (c.sz.tab + 255) / 256 > (size_t)2147483647)
+    throw InputError("polar_ewald_field_grid: the grid is too large for the k-vector table's stage-1 launch");
+  h->d_eg_tab.ensure(c.sz.tab); h->d_eg_t.ensure(c.sz.t); h->d_eg_first.ensure(c.plan.first.size());
+  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
+  if (!h->ev_fa_k.e) h->ev_fa_k.create();
+  HIPCHECK(hipMemcpyAsync(h->d_eg_first.p, c.plan.first.data(), c.plan.first.size() * sizeof(int), hipMemcpyHostToDevice, s));
+  HIPCHECK(hipEventRecord(h->ev_fa[1], s));
+  k_ew_grid_tab<<<(unsigned)((c.sz.tab + 255) / 256), 256, 0, s>>>(c.sz.tab, g, c.plan.kmax, c.plan.lmax, c.sz.off_y, c.sz.off_z, h->d_eg_tab.p);
+  if (nrow > 0)
+    k_ew_grid_l<<<nrow * nzb, 64, 0, s>>>(nrow, n[2], nzb, c.plan.lmax, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_eg_tab.p + c.sz.off_z, h->d_eg_t.p);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa_k, s));
+  HIPCHECK(hipStreamSynchronize(s));   // (c.plan.first has gone up)
+  float tk = 0.f;
+  HIPCHECK(hipEventElapsedTime(&tk, h->ev_fa[1], h->ev_fa_k));
+  h->ew_fa_ms[1] += (double)tk;
+  if (ms) *ms += (double)tk;
+}
+
+// ... and one pass, the points [p0, p0 + m) of the flat order: k_ew_grid_points writes them into d_fa_x, k_ew_point_real adds
+// the real-space static sums and the induced sums as for polar_ewald_field_at; then, per run of whole lines whose V stays within
+// 64 MB (ew_grid_runs), stage 2 (k_ew_grid_k) and stage 3 with the fold (k_ew_grid_h).  Nothing of the handle's step state is
+// written.
+void ewald_field_grid_pass(polar_handle *h, const EwGridCall &c, long long p0, int m, double *x_out, double *e_static, double *e_induced,
+                           double *phi_static, double *phi_induced, double *ms) {
+  const bool phi = phi_static || phi_induced;
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  h->d_fa_x.ensure(3 * mm); h->d_fa_out.ensure(8 * mm);
+  k_ew_grid_points<<<nblk(m, 256), 256, 0, s>>>(m, p0, c.g, h->d_fa_x.p);
+  HIPCHECK(hipGetLastError());
+  ew_point_real_launch(h, m, nullptr, nullptr, phi);
+  const double g = h->P.g_ewald, e2s = std::sqrt(h->P.qqrd2e);
+  const FieldAtOut out{h->d_fa_out.p};
+  const double vol = h->box.prd[0] * h->box.prd[1] * h->box.prd[2];
+  const double qterm = -3.14159265358979323846 / (g * g * vol);
+  const int nx = c.g.n[0], ny = c.g.n[1], nz = c.g.n[2], hmax = c.plan.hmax;
+  const std::vector<EwGridRun> runs = ew_grid_runs(p0, m, nx, c.lines_per_run);
+  long long nl_max = 1;
+  for (const EwGridRun &r : runs) nl_max = std::max(nl_max, r.lb - r.la);
+  h->d_eg_v.ensure((size_t)nl_max * (size_t)(hmax + 1) * 4);
+  const int nyb = nblk(ny, 64), nxb = nblk(nx, 64);
+  for (const EwGridRun &r : runs) {
+    const int nl = (int)(r.lb - r.la), gz0 = (int)(r.la / ny), ngz = (int)((r.lb - 1) / ny) - gz0 + 1;
+    const long long bk = (long long)(hmax + 1) * ngz * nyb, bh = (long long)nl * nxb;
+    if (bk > 2147483647LL || bh > 2147483647LL) throw InputError("polar_ewald_field_grid: a run of lines is too large for one launch");
+    k_ew_grid_k<<<(unsigned)bk, 64, 0, s>>>(r.la, r.lb, gz0, ngz, nyb, nz, ny, c.plan.kmax, h->d_eg_first.p, h->d_ew_rows.p, h->d_eg_t.p,
+                                           h->d_eg_tab.p + c.sz.off_y, h->d_eg_v.p);
+    if (phi) k_ew_grid_h<true><<<(unsigned)bh, 64, 0, s>>>(r.q0, r.q1, r.la, nl, nx, nxb, hmax, h->d_eg_v.p, h->d_eg_tab.p, p0, m, e2s, qterm, h->d_fa_q.p, out);
+    else     k_ew_grid_h<false><<<(unsigned)bh, 64, 0, s>>>(r.q0, r.q1, r.la, nl, nx, nxb, hmax, h->d_eg_v.p, h->d_eg_tab.p, p0, m, e2s, qterm, h->d_fa_q.p, out);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa_k, s));
+  if (x_out) HIPCHECK(hipMemcpyAsync(x_out, h->d_fa_x.p, 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
   if (e_static) HIPCHECK(hipMemcpyAsync(e_static, out.es(), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
   if (e_induced) HIPCHECK(hipMemcpyAsync(e_induced, out.ei(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
   if (phi_static) HIPCHECK(hipMemcpyAsync(phi_static, out.ps(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
