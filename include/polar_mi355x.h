@@ -388,6 +388,51 @@ int polar_ewald_field_grid(polar_handle *h, const int n[3], const double offset[
                            double *e_static, double *e_induced /* [npts][3] each */,
                            double *phi_static, double *phi_induced /* [npts] each */, double *device_ms);
 
+/* ---- LJ, Coulomb and induction energy of test sites (extension) ---------------
+ * What a guest site at a point costs, by the style's own rules and on the device: an adsorption-energy map of a pore, Widom
+ * insertion energies, the energy of a trial placement of a rigid guest.  A point p carries a type t_p (1 .. ntypes), a charge
+ * q_p, a polarizability alpha_p and -- as in polar_field_at -- optionally a skip_atom and a molecule id.  With d = x_p - x_j taken
+ * with the mode's image rule (polar_field_at), r = |d| and the tables of polar_set_types / the pair_coeff text calls (so
+ * `pair_modify shift yes` and every mixing rule are whatever the handle was given):
+ *   e_lj       = sum_j [ r^-6 (lj3[t_p][t_j] r^-6 - lj4[t_p][t_j]) - offset[t_p][t_j] ]   over r^2 < cut_ljsq[t_p][t_j]: strict, as
+ *                PS.cpp:283-286 / 310-314 (the single pair: PS.cpp:1071 / 1090, pair_host.hpp:332 / 345) and the LJ/Coulomb rows have it.  The sum covers ALL atoms: charged,
+ *                polarizable and the inert ones with neither.  The skip_atom adds nothing; an atom of the point's non-zero
+ *                molecule id adds nothing (`neigh_modify exclude molecule/intra`, which the style's inputs run with: the rule of
+ *                polar_field_at's static sums); an atom at r^2 == 0 adds nothing.  special_lj does not enter: a probe has no bonds.
+ *   f_lj[3]    = sum_j (lj1 r^-6 - lj2) r^-6 r^-2 d   over the same atoms: the LJ force on the probe, -grad_p e_lj away from the
+ *                cutoff shells
+ *   e_total[3] = e_static + e_induced: one add per component of exactly what the handle's field call returns at the point with the
+ *                same skip_atom / molecule -- polar_field_at with polar_ewald == 0, polar_ewald_field_at with polar_ewald > 0
+ *   e_coul     = (q_p e2s) (phi_static + phi_induced) of that same field call, grouped as written
+ *   e_pol      = -0.5 alpha_p fma(ex, ex, fma(ey, ey, ez ez)),  e = e_total
+ * r2inv = 1.0 / rsq is the IEEE division, r6inv = r2inv r2inv r2inv (csrc/polar_probe_pair.hpp).
+ * The energy of a site is e_lj + e_coul + e_pol, in LAMMPS energy units.  It is FIRST ORDER: the framework's dipoles are the ones
+ * the last step left (no back-polarization by the guest), the site's own induced dipole alpha_p e_total is relaxed in that frozen
+ * field, and the sites of one call do not see each other.
+ * Nulls: q == NULL and alpha == NULL mean 0 for every point; type may be NULL when neither e_lj nor f_lj is asked for; skip_atom,
+ * molecule as in polar_field_at; any output may be NULL.  The field half (the handle's field pass, potentials included) is
+ * skipped when none of e_coul, e_pol, e_total is asked for, the LJ half when neither e_lj nor f_lj is.  device_ms (may be NULL):
+ * device time of the call's kernels.  All pointers are host pointers; synchronous on return.
+ * Passes of POLAR_FIELD_AT_CHUNK points as in the field calls; a point's bits depend on the point, the records and the tables
+ * alone -- not on the pass, on the other points, on their order, on whether f_lj was asked for or on which half ran beside -- and
+ * the handle is not disturbed: the next compute gives the bits it would have given without the call.  The pass buffers (the field
+ * call's and 92 bytes per point more) and a 4-byte type per atom are freed when the next step begins.  Points outside a periodic
+ * box wrap as in polar_field_at.  npoints == 0 is a no-op.
+ * Which atoms the LJ walk meets: in exact mode every atom at its closest image; in list mode the cells of the list grid a sphere
+ * of the probe type's reach (max_j cut_lj[t_p][t_j]) touches, in both copies of the grid where the inert sites sit behind it.
+ * Call window as polar_field_at: POLAR_ERR_STATE outside it.
+ * POLAR_ERR_UNSUPPORTED: a row-sharded handle; the lab build's tile sweep; list mode in a box with a non-periodic direction; and,
+ * when e_lj or f_lj is asked for, an LJ reach the walk does not cover: in list mode max cut_lj > max(cut_coul, dd_cutoff), in
+ * exact mode a periodic perpendicular box width < 2 max cut_lj (a second image of an atom could lie within reach; a non-periodic
+ * direction has no rule).  The field-only call is still served there.
+ * POLAR_ERR_INPUT: everything polar_field_at refuses; a type outside [1, ntypes]; type == NULL while e_lj or f_lj is asked for;
+ * a non-finite q or alpha, or alpha < 0. */
+int polar_probe_at(polar_handle *h, long long npoints, const double *x /*[npoints][3]*/,
+                   const int *type /*[npoints], 1..ntypes*/, const double *q /*[npoints] or NULL = 0*/,
+                   const double *alpha /*[npoints] or NULL = 0*/, const int *skip_atom, const int *molecule,
+                   double *e_lj, double *e_coul, double *e_pol /*[npoints] each*/,
+                   double *f_lj, double *e_total /*[npoints][3] each*/, double *device_ms);
+
 
 /* ---- stepwise / sharded interface (multi-GPU driver: one process per GPU, rows sharded) ------
  * The reference is single-process only (README.md:5; its pack_comm/unpack_comm are dead code,

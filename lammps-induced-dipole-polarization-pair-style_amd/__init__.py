@@ -142,6 +142,7 @@ EXPORTS = {
     "polar_field_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "polar_ewald_field_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "polar_ewald_field_grid": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "polar_probe_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp]),
     "polar_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "polar_set_row_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "polar_set_global_count": (C.c_int, [C.c_void_p, C.c_longlong]),
@@ -564,6 +565,59 @@ class PolarPair:
         out = self._grid_shaped(out, nx, ny, nz)
         out["x"] = x.reshape(nz, ny, nx, 3)
         return out
+
+    # ---- what a guest site costs at arbitrary points ----
+    def probe_at(self, x, type, q=None, alpha=None, skip_atom=None, molecule=None, force=False):
+        """LJ, Coulomb and first-order induction energy of test sites at the points ``x`` [m, 3] (polar_probe_at in
+        include/polar_mi355x.h: formulas, units, when the call is valid).  ``type`` (1 .. ntypes), ``q``, ``alpha``: per point or
+        a scalar for all; ``skip_atom`` / ``molecule`` as in ``field_at``.  Returns a dict: e_lj, e_coul, e_pol, energy (their
+        sum) [m], e_total [m, 3], f_lj [m, 3] (None without ``force``), ms.  ``type=None`` skips the LJ half (e_lj = 0, the
+        field call alone); ``q=None`` and ``alpha=None`` together skip the field half (e_coul = e_pol = 0, e_total None)."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        m = len(x)
+        per_point = lambda v, dt: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (m,)))
+        ty, qq, al = per_point(type, np.int32), per_point(q, np.float64), per_point(alpha, np.float64)
+        sk, mo = per_point(skip_atom, np.int32), per_point(molecule, np.int32)
+        lj, field = ty is not None, not (qq is None and al is None)
+        if force and not lj:
+            raise ValueError("force=True needs the types of the points")
+        elj, ec, ep = np.zeros(m), np.zeros(m), np.zeros(m)
+        et = np.zeros((m, 3)) if field else None
+        fl = np.zeros((m, 3)) if force else None
+        ms = C.c_double()
+        dptr = lambda a: None if a is None else _dptr(a)
+        iptr = lambda a: None if a is None else _iptr(a)
+        self._ck(self.L.polar_probe_at(self.h, m, _dptr(x), iptr(ty), dptr(qq), dptr(al), iptr(sk), iptr(mo), _dptr(elj) if lj else None,
+                                       _dptr(ec) if field else None, _dptr(ep) if field else None, dptr(fl), dptr(et), C.byref(ms)))
+        return dict(e_lj=elj, e_coul=ec, e_pol=ep, energy=elj + ec + ep, e_total=et, f_lj=fl, ms=ms.value)
+
+    def probe_grid(self, shape, type, q=0.0, alpha=0.0):
+        """``probe_at`` on the (nx, ny, nz) grid of ``field_grid`` (``grid_points``): an adsorption-energy map of the box for one
+        kind of site.  The arrays come back as (nz, ny, nx[, 3])."""
+        nx, ny, nz = (int(v) for v in shape)
+        out = self.probe_at(self.grid_points((nx, ny, nz)), type, q, alpha)
+        for k in ("e_lj", "e_coul", "e_pol", "energy"):
+            out[k] = out[k].reshape(nz, ny, nx)
+        if out["e_total"] is not None:
+            out["e_total"] = out["e_total"].reshape(nz, ny, nx, 3)
+        return out
+
+    def insertion_energy(self, sites, type, q, alpha, molecule=None, skip_atom=None):
+        """Trial insertions of a rigid guest: ``sites`` [ntrial, nsite, 3]; ``type``, ``q``, ``alpha`` per site of the guest
+        ([nsite]) or scalars.  One ``probe_at`` call over all sites; returns the per-trial sums e_lj, e_coul, e_pol, energy
+        [ntrial] and ms.  ``molecule`` / ``skip_atom``: one per trial (or a scalar), handed to each of its sites -- for
+        re-inserting a guest that is in the box.  First order: the sites of a guest do not see each other."""
+        sites = np.ascontiguousarray(sites, dtype=np.float64)
+        assert sites.ndim == 3 and sites.shape[2] == 3
+        nt, ns = sites.shape[:2]
+        per_site = lambda v, dt: None if v is None else np.broadcast_to(np.asarray(v, dtype=dt), (nt, ns)).reshape(-1)
+        per_trial = lambda v: None if v is None else np.broadcast_to(np.asarray(v, dtype=np.int32).reshape(-1, 1) if np.ndim(v) else np.asarray(v, dtype=np.int32), (nt, ns)).reshape(-1)
+        out = self.probe_at(sites.reshape(-1, 3), per_site(type, np.int32), per_site(q, np.float64), per_site(alpha, np.float64),
+                            per_trial(skip_atom), per_trial(molecule))
+        res = {k: out[k].reshape(nt, ns).sum(axis=1) for k in ("e_lj", "e_coul", "e_pol")}
+        res["energy"] = res["e_lj"] + res["e_coul"] + res["e_pol"]
+        res["ms"] = out["ms"]
+        return res
 
     @staticmethod
     def _grid_shaped(out, nx, ny, nz):

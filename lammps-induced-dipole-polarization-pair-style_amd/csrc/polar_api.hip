@@ -20,6 +20,11 @@ void upload_types(polar_handle *h, int ntypes, const double *const t[7]) {
   h->types_set = true;
   h->r_cmax = r_cmax;
   h->skin_valid = false;
+  // polar_probe_at: the table on the host, and how far a probe of every type reaches
+  h->lj_host = pack;
+  h->probe_reach_max = probe_reach(ntypes, h->lj_host.data(), h->probe_reach);
+  h->d_pr_reach.ensure(h->probe_reach.size());
+  HIPCHECK(hipMemcpy(h->d_pr_reach.p, h->probe_reach.data(), h->probe_reach.size() * sizeof(double), hipMemcpyHostToDevice));
 }
 
 void upload_coul(polar_handle *h, double g_ewald, double qqrd2e, const double *slj, const double *scoul, int nbits,
@@ -806,6 +811,47 @@ int polar_ewald_field_at(polar_handle *h, long long npoints, const double *x, co
       ewald_field_at_pass(h, m, x + 3 * p0, skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr,
                           e_static ? e_static + 3 * p0 : nullptr, e_induced ? e_induced + 3 * p0 : nullptr,
                           phi_static ? phi_static + p0 : nullptr, phi_induced ? phi_induced + p0 : nullptr, device_ms);
+    }
+    return (int)POLAR_OK;
+  });
+}
+
+/* ---- LJ, Coulomb and induction energy of test sites (polar_probe_at.hpp) -------- */
+int polar_probe_at(polar_handle *h, long long npoints, const double *x, const int *type, const double *q, const double *alpha,
+                   const int *skip_atom, const int *molecule, double *e_lj, double *e_coul, double *e_pol, double *f_lj,
+                   double *e_total, double *device_ms) {
+  return guarded(h, [&]() {
+    need_device(h);
+    const polar_settings &st = h->ph.st;
+    const bool list = st.dd_cutoff > 0.0, lj = e_lj || f_lj, field = e_coul || e_pol || e_total;
+    if (sharded(h)) throw Unsupported("polar_probe_at: not offered on a row-sharded handle");
+    if (tile_mode(h)) throw Unsupported("polar_probe_at: not offered with the tile sweep (lab build)");
+    if (!h->field_ready) throw std::runtime_error("polar_probe_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
+    if (list && !(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2]))
+      throw Unsupported("polar_probe_at: list mode (dd_cutoff > 0) needs a box periodic in every direction");
+    if (npoints < 0) throw InputError("polar_probe_at: negative point count");
+    if (device_ms) *device_ms = 0.0;
+    if (ewald_on(h)) h->ew_fa_ms[0] = h->ew_fa_ms[1] = 0.0;
+    if (npoints == 0) return (int)POLAR_OK;
+    if (!x) throw InputError("polar_probe_at: null pointer");
+    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
+    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    check_probe_sites(npoints, type, h->ntypes, q, alpha, lj);
+    if (lj) {
+      double width[3];
+      box_widths(h->box, width);
+      check_probe_reach(list, h->probe_reach_max, st.cut_coul, st.dd_cutoff, width, h->box.periodic);
+    }
+    if (!lj && !field) return (int)POLAR_OK;
+    HIPCHECK(hipSetDevice(h->device));
+    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
+    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
+    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
+      const int m = (int)std::min(chunk, npoints - p0);
+      probe_at_pass(h, m, x + 3 * p0, type ? type + p0 : nullptr, q ? q + p0 : nullptr, alpha ? alpha + p0 : nullptr,
+                    skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr, e_lj ? e_lj + p0 : nullptr,
+                    e_coul ? e_coul + p0 : nullptr, e_pol ? e_pol + p0 : nullptr, f_lj ? f_lj + 3 * p0 : nullptr,
+                    e_total ? e_total + 3 * p0 : nullptr, device_ms);
     }
     return (int)POLAR_OK;
   });

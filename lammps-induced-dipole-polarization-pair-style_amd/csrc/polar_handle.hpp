@@ -330,6 +330,14 @@ struct polar_handle {
   // the first row of every h (freed with the pass buffers)
   DBuf<double2> d_eg_tab, d_eg_t, d_eg_v;
   DBuf<int> d_eg_first;
+  // polar_probe_at (polar_probe_at.hpp): the host copy of the packed LJ table and the reach of every type in it (upload_types:
+  // once per polar_set_types), the reach on the device; per call window the type of every record (made by the first call, dropped
+  // with the pass buffers); one pass's {q | alpha}, its types and its results (9 doubles per point)
+  std::vector<double> lj_host, probe_reach;
+  double probe_reach_max = 0.0;
+  DBuf<double> d_pr_reach, d_pr_qa, d_pr_out;
+  DBuf<int> d_pr_type, d_pr_type_s;
+  bool pr_types_valid = false;
   double ew_field_ms = 0.0;   // device time of the last step's ewald_field (S(k) and k_ew_field): polar_pair_extract "ewald_field_ms"
   // Everything above frees itself.  What is left to do first: let the device finish with it.
   ~polar_handle() {
@@ -528,11 +536,16 @@ void step_begin_finish(polar_handle *h);                        // ... and from 
 void build_cluster_lists(polar_handle *h);
 // one pass of polar_field_at: m points (host arrays; skip_atom, molecule and every output may be null), the kernel's device
 // time added to *ms; synchronous on return
+// (phi_on_device: the potentials are computed into the pass's field block although the caller takes neither home)
 void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
-                   double *e_induced, double *phi_static, double *phi_induced, double *ms);
+                   double *e_induced, double *phi_static, double *phi_induced, double *ms, bool phi_on_device = false);
 // the same for polar_ewald_field_at: real-space and induced sums, then the reciprocal sums of the step's k-vectors
 void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
-                         double *e_induced, double *phi_static, double *phi_induced, double *ms);
+                         double *e_induced, double *phi_static, double *phi_induced, double *ms, bool phi_on_device = false);
+// one pass of polar_probe_at: the field half through one of the two passes above (`field`: any of e_coul, e_pol, e_total is
+// asked for), then k_probe_lj (`lj`: e_lj or f_lj is) with the combine step, or k_probe_combine alone
+void probe_at_pass(polar_handle *h, int m, const double *x, const int *type, const double *q, const double *alpha, const int *skip_atom,
+                   const int *molecule, double *e_lj, double *e_coul, double *e_pol, double *f_lj, double *e_total, double *ms);
 // polar_ewald_field_grid: what the passes of a call share -- the grid, the layout of the tables and of the scratch
 // (polar_plan.hpp) and the lines of V per run.  ewald_field_grid_begin fills it, builds the phase tables and runs stage 1 on
 // the device (their time goes to the reciprocal share); ewald_field_grid_pass handles the points [p0, p0 + m) of the flat order:

@@ -40,3 +40,4 @@
 #include "polar_field_at.hpp"   // the field and the potential of the polarized box at arbitrary points (polar_field_at)
 #include "polar_ewald_field_at.hpp"   // ... with `polar_ewald`: the Ewald field and potential (polar_ewald_field_at)
 #include "polar_ewald_field_grid.hpp" // ... on a regular grid of the cell (polar_ewald_field_grid)
+#include "polar_probe_at.hpp"         // LJ, Coulomb and induction energy of test sites (polar_probe_at)

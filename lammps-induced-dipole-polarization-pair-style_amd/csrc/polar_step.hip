@@ -730,6 +730,7 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
   h->d_fa_x.release(); h->d_fa_idx.release(); h->d_fa_out.release();   // a probe's pass buffers (100 bytes per point) do not outlive the step it looked at
   h->d_fa_part.release(); h->ew_q_valid = false;   // (polar_ewald_field_at: its chunk partials; the charges may be other ones)
   h->d_eg_tab.release(); h->d_eg_t.release(); h->d_eg_v.release(); h->d_eg_first.release();   // (polar_ewald_field_grid: tables, T, V)
+  h->d_pr_qa.release(); h->d_pr_type.release(); h->d_pr_out.release(); h->d_pr_type_s.release(); h->pr_types_valid = false;   // (polar_probe_at: sites, results, the records' types)
   if (!h->types_set || !h->coul_set) throw std::runtime_error("polar_compute before the pair tables were set: polar_pair_init (or polar_set_types), then polar_set_coul with the Coulomb tables of Pair::init_tables unless pair_modify table 0");
   if (!h->box_set || !h->atoms_set || !h->neigh_set) throw std::runtime_error("polar_compute before polar_set_box/polar_set_atoms/polar_set_neighbors");
   const polar_settings &st = h->ph.st;
@@ -1160,11 +1161,11 @@ void step_begin_finish(polar_handle *h) {
 // records, the molecule ids and -- list mode -- the cell table the finished step left, the results the caller asked for come
 // back.  Nothing of the handle's step state is written.
 void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
-                   double *e_induced, double *phi_static, double *phi_induced, double *ms) {
+                   double *e_induced, double *phi_static, double *phi_induced, double *ms, bool phi_on_device) {
   const polar_settings &st = h->ph.st;
   const bool ap = !(st.dd_cutoff > 0.0);
   const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
-  const bool phi = phi_static || phi_induced;
+  const bool phi = phi_static || phi_induced || phi_on_device;
   hipStream_t s = h->stream;
   const size_t mm = (size_t)m;
   h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fa_out.ensure(8 * mm);
@@ -1245,8 +1246,8 @@ static void ew_point_real_launch(polar_handle *h, int m, const int *d_skip, cons
 // (points, row chunks of the step's k-vector table) and k_ew_point_fold.  S(k) in d_ew_s is the finished step's: nothing writes
 // it after ewald_field.  Nothing of the handle's step state is written.
 void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *e_static,
-                         double *e_induced, double *phi_static, double *phi_induced, double *ms) {
-  const bool phi = phi_static || phi_induced;
+                         double *e_induced, double *phi_static, double *phi_induced, double *ms, bool phi_on_device) {
+  const bool phi = phi_static || phi_induced || phi_on_device;
   hipStream_t s = h->stream;
   const size_t mm = (size_t)m;
   h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fa_out.ensure(8 * mm);
@@ -1290,6 +1291,75 @@ void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *ski
   HIPCHECK(hipEventElapsedTime(&tk, h->ev_fa[1], h->ev_fa_k));
   h->ew_fa_ms[0] += (double)t; h->ew_fa_ms[1] += (double)tk;
   if (ms) *ms += (double)t + (double)tk;
+}
+
+// polar_probe_at, one pass.  The field half is a pass of the handle's own field call with no host output: it leaves the points,
+// skip_atom and molecule in d_fa_x / d_fa_idx and the field block (potentials included) in d_fa_out, and has synchronised.  Then
+// one launch: k_probe_lj (polar_probe_at.hpp), whose lane 0 also combines the field block with the site's q and alpha, or
+// k_probe_combine alone.  Nothing of the handle's step state is written; the records' types (d_pr_type_s) are made by the first
+// pass of a call window.
+void probe_at_pass(polar_handle *h, int m, const double *x, const int *type, const double *q, const double *alpha, const int *skip_atom,
+                   const int *molecule, double *e_lj, double *e_coul, double *e_pol, double *f_lj, double *e_total, double *ms) {
+  const polar_settings &st = h->ph.st;
+  const bool ap = !(st.dd_cutoff > 0.0);
+  const bool lj = e_lj || f_lj, field = e_coul || e_pol || e_total;
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  if (field) {
+    if (ewald_on(h)) ewald_field_at_pass(h, m, x, skip_atom, molecule, nullptr, nullptr, nullptr, nullptr, ms, true);
+    else field_at_pass(h, m, x, skip_atom, molecule, nullptr, nullptr, nullptr, nullptr, ms, true);
+  } else {
+    h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm);
+    if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
+    HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
+    if (skip_atom) HIPCHECK(hipMemcpyAsync(h->d_fa_idx.p, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s));
+    if (molecule) HIPCHECK(hipMemcpyAsync(h->d_fa_idx.p + mm, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s));
+  }
+  const int *d_skip = skip_atom ? h->d_fa_idx.p : nullptr, *d_pmol = molecule ? h->d_fa_idx.p + mm : nullptr;
+  h->d_pr_out.ensure(9 * mm); h->d_pr_qa.ensure(2 * mm); h->d_pr_type.ensure(mm);
+  const double *d_q = nullptr, *d_a = nullptr;
+  if (field && q) { d_q = h->d_pr_qa.p; HIPCHECK(hipMemcpyAsync(h->d_pr_qa.p, q, mm * sizeof(double), hipMemcpyHostToDevice, s)); }
+  if (field && alpha) { d_a = h->d_pr_qa.p + mm; HIPCHECK(hipMemcpyAsync(h->d_pr_qa.p + mm, alpha, mm * sizeof(double), hipMemcpyHostToDevice, s)); }
+  if (lj) HIPCHECK(hipMemcpyAsync(h->d_pr_type.p, type, mm * sizeof(int), hipMemcpyHostToDevice, s));
+  if (lj && !h->pr_types_valid) {   // the records' types, once per call window
+    h->d_pr_type_s.ensure((size_t)h->nlocal + 1);
+    k_probe_types<<<nblk(h->nlocal, 256), 256, 0, s>>>(h->nlocal, h->sorted ? h->d_perm.p : nullptr, h->d_type.p, h->d_pr_type_s.p);
+    HIPCHECK(hipGetLastError());
+    h->pr_types_valid = true;
+  }
+  const ProbeOut out{h->d_pr_out.p};
+  const ProbeField fld{FieldAtOut{field ? h->d_fa_out.p : nullptr}, d_q, d_a, std::sqrt(h->P.qqrd2e)};
+  HIPCHECK(hipEventRecord(h->ev_fa[0], s));
+  if (lj) {
+    ProbeGrid pg;
+    pg.g = h->grid;   // (exact mode has built no grid: the kernel takes the box origin from it in both modes)
+    for (int k = 0; k < 3; k++) pg.g.lo[k] = h->boxlo[k];
+    pg.ncell_inert = (!ap && h->cell_split) ? h->ncell : 0;
+    double width[3];
+    box_widths(h->box, width);
+    probe_dfrac_scale(width, pg.dscale);
+    const dim3 grid(nblk(m, POLAR_ROWS_PER_BLOCK)), block(POLAR_BLOCK);
+#define PR(AP, F)                                                                                                                   \
+  k_probe_lj<AP, F><<<grid, block, 0, s>>>(m, h->d_fa_x.p, h->d_pr_type.p, d_skip, d_pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal, \
+                                           h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_pr_type_s.p, h->d_mol_s.p, h->box, pg,        \
+                                           AP ? nullptr : h->d_cell_first.p, h->d_lj.p, h->ntypes, h->d_pr_reach.p, fld, out)
+    if (ap) { if (f_lj) PR(true, true); else PR(true, false); }
+    else    { if (f_lj) PR(false, true); else PR(false, false); }
+#undef PR
+  } else {
+    k_probe_combine<<<nblk(m, 256), 256, 0, s>>>(m, fld, out);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa[1], s));
+  if (e_lj) HIPCHECK(hipMemcpyAsync(e_lj, out.elj(), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (f_lj) HIPCHECK(hipMemcpyAsync(f_lj, out.flj(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (e_total) HIPCHECK(hipMemcpyAsync(e_total, out.et(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (e_coul) HIPCHECK(hipMemcpyAsync(e_coul, out.ec(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (e_pol) HIPCHECK(hipMemcpyAsync(e_pol, out.ep(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  float t = 0.f;
+  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
+  if (ms) *ms += (double)t;
 }
 
 // polar_ewald_field_grid, once per call: the layout from the k-vector table (its rows come back from the device: 16 bytes per
