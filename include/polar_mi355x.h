@@ -433,6 +433,48 @@ int polar_probe_at(polar_handle *h, long long npoints, const double *x /*[npoint
                    double *e_lj, double *e_coul, double *e_pol /*[npoints] each*/,
                    double *f_lj, double *e_total /*[npoints][3] each*/, double *device_ms);
 
+/* ---- the gradient of the field at points, and the full force on a test site (extension) ---------------
+ * polar_field_grad_at: polar_field_at's two fields together with their gradients G_ab = d e_a / d x_b at the points -- what a
+ * point quadrupole couples to, and what the induction force on a polarizable site needs.  Both gradients are symmetric
+ * (-grad phi = e holds for both parts); six components each, in the order xx, yy, zz, xy, xz, yz.  With d, r, e2s, rc, s3, s5 and
+ * the atoms of each sum exactly as in polar_field_at (the same image rule, cutoffs, molecule rule, skip_atom, r == 0 rule):
+ *   g_static_ab  = e2s sum_j q_j [ (r^-3 - rc^-2 r^-1) delta_ab + (rc^-2 r^-3 - 3 r^-5) d_a d_b ]
+ *                  (trace: -2 e2s sum_j q_j / (rc^2 r) -- the shifted-force field is not harmonic)
+ *   g_induced_ab = sum_j [ s5 (mu_a d_b + d_a mu_b + (mu_j.d) delta_ab) - s7 (mu_j.d) d_a d_b ],   s7 = -(1/r) d s5 / d r:
+ *                  damping `none`: 15 r^-7 (the gradient is traceless); exponential damping, a = polar_damp r:
+ *                  15 r^-7 (1 - e^-a (1 + a + a^2/2 + a^3/6 + a^4/30))
+ *   e_static, e_induced: polar_field_at's, bit for bit, at the same points with the same skip_atom / molecule
+ * Units: those of ef_static per distance unit.  Both gradients jump across their cutoff shell (r = rc; r = dd_cutoff in list
+ * mode) and, in exact mode, where a pair's nearest image flips.
+ * Any output may be NULL.  device_ms, host pointers, synchronous return, passes of POLAR_FIELD_AT_CHUNK points, the wrap of far
+ * points and npoints == 0 as in polar_field_at; a point's bits depend on the point and the records alone (no atomics), and the
+ * handle is not disturbed.  The pass buffers (polar_field_at's points and 192 bytes per point of a pass) are freed when the
+ * next step begins.
+ * Call window and errors are polar_field_at's: POLAR_ERR_STATE outside the window; POLAR_ERR_UNSUPPORTED on a row-sharded handle,
+ * with the lab build's tile sweep, in list mode in a box with a non-periodic direction, and with polar_ewald > 0 (the gradient of
+ * the real-space erfc part and of the reciprocal part is not built yet); POLAR_ERR_INPUT as polar_field_at. */
+int polar_field_grad_at(polar_handle *h, long long npoints, const double *x /*[npoints][3]*/, const int *skip_atom,
+                        const int *molecule, double *g_static, double *g_induced /* [npoints][6] each */,
+                        double *e_static, double *e_induced /* [npoints][3] each, may be NULL */, double *device_ms);
+
+/* polar_probe_force_at: the force on a site of type t_p, charge q_p and polarizability alpha_p at each point, in the frozen
+ * framework -- first order, as polar_probe_at: minus the gradient of that call's e_lj + e_coul + e_pol away from the cutoff shells
+ * (and, in exact mode, the image flips).  With e = e_static + e_induced and G = g_static + g_induced of polar_field_grad_at at
+ * the point, one add per component:
+ *   f_lj[3]   = polar_probe_at's f_lj, bit for bit (that call's kernel and its reach check)
+ *   f_coul[3] = (q_p e2s) e
+ *   f_pol_b   = alpha_p fma(e_x, G_xb, fma(e_y, G_yb, e_z G_zb))        (= -d/dx_b of -1/2 alpha_p |e|^2; G is symmetric)
+ * in LAMMPS energy units per distance unit.  The torque on a rigid guest follows from the forces on its sites.
+ * Nulls: q == NULL / alpha == NULL mean 0 for every point; type may be NULL when f_lj is not asked for; any output may be NULL (the
+ * LJ pass runs only for f_lj, the gradient pass only for f_coul or f_pol).  Passes, bits, buffers, the wrap of far points and
+ * npoints == 0 as above.
+ * Call window, POLAR_ERR_UNSUPPORTED and POLAR_ERR_INPUT are polar_probe_at's (the LJ reach rule applies when f_lj is asked
+ * for), and POLAR_ERR_UNSUPPORTED with polar_ewald > 0 as for polar_field_grad_at. */
+int polar_probe_force_at(polar_handle *h, long long npoints, const double *x /*[npoints][3]*/,
+                         const int *type /*[npoints], 1..ntypes*/, const double *q /*[npoints] or NULL = 0*/,
+                         const double *alpha /*[npoints] or NULL = 0*/, const int *skip_atom, const int *molecule,
+                         double *f_lj, double *f_coul, double *f_pol /*[npoints][3] each*/, double *device_ms);
+
 
 /* ---- stepwise / sharded interface (multi-GPU driver: one process per GPU, rows sharded) ------
  * The reference is single-process only (README.md:5; its pack_comm/unpack_comm are dead code,

@@ -143,6 +143,8 @@ EXPORTS = {
     "polar_ewald_field_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "polar_ewald_field_grid": (C.c_int, [C.c_void_p, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "polar_probe_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "polar_field_grad_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
+    "polar_probe_force_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]),
     "polar_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "polar_set_row_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "polar_set_global_count": (C.c_int, [C.c_void_p, C.c_longlong]),
@@ -618,6 +620,68 @@ class PolarPair:
         res["energy"] = res["e_lj"] + res["e_coul"] + res["e_pol"]
         res["ms"] = out["ms"]
         return res
+
+    # ---- the gradient of the field, and the force on a guest site ----
+    def field_grad_at(self, x, skip_atom=None, molecule=None, field=True):
+        """Gradient of the static and of the induced field at the points ``x`` [m, 3] (polar_field_grad_at in
+        include/polar_mi355x.h: formulas, units, when the call is valid); ``skip_atom`` / ``molecule`` as in ``field_at``.
+        Returns a dict: g_static, g_induced [m, 6] (xx, yy, zz, xy, xz, yz), e_static, e_induced [m, 3] (the bits of
+        ``field_at``; None without ``field``), ms."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        m = len(x)
+        sk = None if skip_atom is None else np.ascontiguousarray(skip_atom, dtype=np.int32)
+        mo = None if molecule is None else np.ascontiguousarray(molecule, dtype=np.int32)
+        assert (sk is None or sk.shape == (m,)) and (mo is None or mo.shape == (m,))
+        gs, gi = np.zeros((m, 6)), np.zeros((m, 6))
+        es, ei = (np.zeros((m, 3)), np.zeros((m, 3))) if field else (None, None)
+        ms = C.c_double()
+        self._ck(self.L.polar_field_grad_at(self.h, m, _dptr(x), None if sk is None else _iptr(sk), None if mo is None else _iptr(mo),
+                                            _dptr(gs), _dptr(gi), None if es is None else _dptr(es), None if ei is None else _dptr(ei),
+                                            C.byref(ms)))
+        return dict(g_static=gs, g_induced=gi, e_static=es, e_induced=ei, ms=ms.value)
+
+    def field_grad_grid(self, shape, field=True):
+        """``field_grad_at`` on the (nx, ny, nz) grid of ``field_grid`` (``grid_points``); the arrays come back as
+        (nz, ny, nx, 6) and (nz, ny, nx, 3)."""
+        nx, ny, nz = (int(v) for v in shape)
+        out = self.field_grad_at(self.grid_points((nx, ny, nz)), field=field)
+        for k, w in (("g_static", 6), ("g_induced", 6), ("e_static", 3), ("e_induced", 3)):
+            if out[k] is not None:
+                out[k] = out[k].reshape(nz, ny, nx, w)
+        return out
+
+    def probe_force_at(self, x, type, q=None, alpha=None, skip_atom=None, molecule=None):
+        """The force on test sites at the points ``x`` [m, 3] in the frozen framework (polar_probe_force_at in
+        include/polar_mi355x.h); arguments as ``probe_at``.  Returns a dict: f_lj, f_coul, f_pol, force (their sum) [m, 3], ms.
+        ``type=None`` skips the LJ part (f_lj = 0); ``q=None`` and ``alpha=None`` together skip the field part."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
+        m = len(x)
+        per_point = lambda v, dt: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (m,)))
+        ty, qq, al = per_point(type, np.int32), per_point(q, np.float64), per_point(alpha, np.float64)
+        sk, mo = per_point(skip_atom, np.int32), per_point(molecule, np.int32)
+        lj, field = ty is not None, not (qq is None and al is None)
+        fl, fc, fp = np.zeros((m, 3)), np.zeros((m, 3)), np.zeros((m, 3))
+        ms = C.c_double()
+        dptr = lambda a: None if a is None else _dptr(a)
+        iptr = lambda a: None if a is None else _iptr(a)
+        self._ck(self.L.polar_probe_force_at(self.h, m, _dptr(x), iptr(ty), dptr(qq), dptr(al), iptr(sk), iptr(mo), _dptr(fl) if lj else None,
+                                             _dptr(fc) if field else None, _dptr(fp) if field else None, C.byref(ms)))
+        return dict(f_lj=fl, f_coul=fc, f_pol=fp, force=fl + fc + fp, ms=ms.value)
+
+    def insertion_force(self, sites, type, q, alpha, centre=None, molecule=None, skip_atom=None):
+        """Net force and torque on trial placements of a rigid guest: ``sites`` [ntrial, nsite, 3] and the other arguments as
+        ``insertion_energy``; ``centre`` [ntrial, 3] (or [3]): the point the torque is taken about, by default the mean of the
+        trial's sites.  One ``probe_force_at`` call; returns force, torque [ntrial, 3], site_force [ntrial, nsite, 3] and ms."""
+        sites = np.ascontiguousarray(sites, dtype=np.float64)
+        assert sites.ndim == 3 and sites.shape[2] == 3
+        nt, ns = sites.shape[:2]
+        per_site = lambda v, dt: None if v is None else np.broadcast_to(np.asarray(v, dtype=dt), (nt, ns)).reshape(-1)
+        per_trial = lambda v: None if v is None else np.broadcast_to(np.asarray(v, dtype=np.int32).reshape(-1, 1) if np.ndim(v) else np.asarray(v, dtype=np.int32), (nt, ns)).reshape(-1)
+        out = self.probe_force_at(sites.reshape(-1, 3), per_site(type, np.int32), per_site(q, np.float64), per_site(alpha, np.float64),
+                                  per_trial(skip_atom), per_trial(molecule))
+        f = out["force"].reshape(nt, ns, 3)
+        c = sites.mean(axis=1) if centre is None else np.broadcast_to(np.asarray(centre, dtype=np.float64), (nt, 3))
+        return dict(force=f.sum(axis=1), torque=np.cross(sites - c[:, None, :], f).sum(axis=1), site_force=f, ms=out["ms"])
 
     @staticmethod
     def _grid_shaped(out, nx, ny, nz):

@@ -857,6 +857,76 @@ int polar_probe_at(polar_handle *h, long long npoints, const double *x, const in
   });
 }
 
+/* ---- the gradient of the field at arbitrary points (polar_field_grad_at.hpp) -------- */
+int polar_field_grad_at(polar_handle *h, long long npoints, const double *x, const int *skip_atom, const int *molecule,
+                        double *g_static, double *g_induced, double *e_static, double *e_induced, double *device_ms) {
+  return guarded(h, [&]() {
+    need_device(h);
+    const polar_settings &st = h->ph.st;
+    if (ewald_on(h)) throw Unsupported("polar_field_grad_at: not offered with polar_ewald (the gradient of the real-space erfc part and of the reciprocal part is a follow-up)");
+    if (sharded(h)) throw Unsupported("polar_field_grad_at: not offered on a row-sharded handle");
+    if (tile_mode(h)) throw Unsupported("polar_field_grad_at: not offered with the tile sweep (lab build)");
+    if (!h->field_ready) throw std::runtime_error("polar_field_grad_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
+    if (st.dd_cutoff > 0.0 && !(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2]))
+      throw Unsupported("polar_field_grad_at: list mode (dd_cutoff > 0) needs a box periodic in every direction");
+    if (npoints < 0) throw InputError("polar_field_grad_at: negative point count");
+    if (device_ms) *device_ms = 0.0;
+    if (npoints == 0) return (int)POLAR_OK;
+    if (!x) throw InputError("polar_field_grad_at: null pointer");
+    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
+    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    HIPCHECK(hipSetDevice(h->device));
+    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
+    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
+    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
+      const int m = (int)std::min(chunk, npoints - p0);
+      field_grad_at_pass(h, m, x + 3 * p0, skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr,
+                         g_static ? g_static + 6 * p0 : nullptr, g_induced ? g_induced + 6 * p0 : nullptr,
+                         e_static ? e_static + 3 * p0 : nullptr, e_induced ? e_induced + 3 * p0 : nullptr, device_ms);
+    }
+    return (int)POLAR_OK;
+  });
+}
+
+/* ---- ... and the force on a test site: LJ, Coulomb, induction (polar_field_grad_at.hpp, polar_probe_at.hpp) -------- */
+int polar_probe_force_at(polar_handle *h, long long npoints, const double *x, const int *type, const double *q, const double *alpha,
+                         const int *skip_atom, const int *molecule, double *f_lj, double *f_coul, double *f_pol, double *device_ms) {
+  return guarded(h, [&]() {
+    need_device(h);
+    const polar_settings &st = h->ph.st;
+    const bool list = st.dd_cutoff > 0.0, lj = f_lj != nullptr, field = f_coul || f_pol;
+    if (ewald_on(h)) throw Unsupported("polar_probe_force_at: not offered with polar_ewald (the gradient of the Ewald field is a follow-up)");
+    if (sharded(h)) throw Unsupported("polar_probe_force_at: not offered on a row-sharded handle");
+    if (tile_mode(h)) throw Unsupported("polar_probe_force_at: not offered with the tile sweep (lab build)");
+    if (!h->field_ready) throw std::runtime_error("polar_probe_force_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
+    if (list && !(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2]))
+      throw Unsupported("polar_probe_force_at: list mode (dd_cutoff > 0) needs a box periodic in every direction");
+    if (npoints < 0) throw InputError("polar_probe_force_at: negative point count");
+    if (device_ms) *device_ms = 0.0;
+    if (npoints == 0) return (int)POLAR_OK;
+    if (!x) throw InputError("polar_probe_force_at: null pointer");
+    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
+    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    check_probe_sites(npoints, type, h->ntypes, q, alpha, lj);
+    if (lj) {   // (polar_probe_at's reach check: f_lj is that call's)
+      double width[3];
+      box_widths(h->box, width);
+      check_probe_reach(list, h->probe_reach_max, st.cut_coul, st.dd_cutoff, width, h->box.periodic);
+    }
+    if (!lj && !field) return (int)POLAR_OK;
+    HIPCHECK(hipSetDevice(h->device));
+    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
+    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
+    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
+      const int m = (int)std::min(chunk, npoints - p0);
+      probe_force_at_pass(h, m, x + 3 * p0, type ? type + p0 : nullptr, q ? q + p0 : nullptr, alpha ? alpha + p0 : nullptr,
+                          skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr, f_lj ? f_lj + 3 * p0 : nullptr,
+                          f_coul ? f_coul + 3 * p0 : nullptr, f_pol ? f_pol + 3 * p0 : nullptr, device_ms);
+    }
+    return (int)POLAR_OK;
+  });
+}
+
 /* ---- ... on a regular grid of the cell: the reciprocal sums as three 1-D transforms (polar_ewald_field_grid.hpp) -------- */
 int polar_ewald_field_grid(polar_handle *h, const int n[3], const double offset[3], double *x_out, double *e_static, double *e_induced,
                            double *phi_static, double *phi_induced, double *device_ms) {

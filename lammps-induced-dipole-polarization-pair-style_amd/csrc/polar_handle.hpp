@@ -338,6 +338,9 @@ struct polar_handle {
   DBuf<double> d_pr_reach, d_pr_qa, d_pr_out;
   DBuf<int> d_pr_type, d_pr_type_s;
   bool pr_types_valid = false;
+  // polar_field_grad_at / polar_probe_force_at (polar_field_grad_at.hpp): one pass's block of fields and gradients and the two
+  // forces made of it (24 doubles per point; freed with the pass buffers)
+  DBuf<double> d_fg_out;
   double ew_field_ms = 0.0;   // device time of the last step's ewald_field (S(k) and k_ew_field): polar_pair_extract "ewald_field_ms"
   // Everything above frees itself.  What is left to do first: let the device finish with it.
   ~polar_handle() {
@@ -546,6 +549,13 @@ void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *ski
 // asked for), then k_probe_lj (`lj`: e_lj or f_lj is) with the combine step, or k_probe_combine alone
 void probe_at_pass(polar_handle *h, int m, const double *x, const int *type, const double *q, const double *alpha, const int *skip_atom,
                    const int *molecule, double *e_lj, double *e_coul, double *e_pol, double *f_lj, double *e_total, double *ms);
+// one pass of polar_field_grad_at: as field_at_pass, with the six components of each gradient; the block stays in d_fg_out
+void field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *g_static,
+                        double *g_induced, double *e_static, double *e_induced, double *ms);
+// one pass of polar_probe_force_at: f_lj through probe_at_pass, f_coul and f_pol through field_grad_at_pass and
+// k_probe_force_combine
+void probe_force_at_pass(polar_handle *h, int m, const double *x, const int *type, const double *q, const double *alpha,
+                         const int *skip_atom, const int *molecule, double *f_lj, double *f_coul, double *f_pol, double *ms);
 // polar_ewald_field_grid: what the passes of a call share -- the grid, the layout of the tables and of the scratch
 // (polar_plan.hpp) and the lines of V per run.  ewald_field_grid_begin fills it, builds the phase tables and runs stage 1 on
 // the device (their time goes to the reciprocal share); ewald_field_grid_pass handles the points [p0, p0 + m) of the flat order:

@@ -41,3 +41,4 @@
 #include "polar_ewald_field_at.hpp"   // ... with `polar_ewald`: the Ewald field and potential (polar_ewald_field_at)
 #include "polar_ewald_field_grid.hpp" // ... on a regular grid of the cell (polar_ewald_field_grid)
 #include "polar_probe_at.hpp"         // LJ, Coulomb and induction energy of test sites (polar_probe_at)
+#include "polar_field_grad_at.hpp"    // the field gradient at points and the force on a test site (polar_field_grad_at, polar_probe_force_at)

@@ -731,6 +731,7 @@ void phase_begin(polar_handle *h, int eflag, int vflag, const double *mu_host) {
   h->d_fa_part.release(); h->ew_q_valid = false;   // (polar_ewald_field_at: its chunk partials; the charges may be other ones)
   h->d_eg_tab.release(); h->d_eg_t.release(); h->d_eg_v.release(); h->d_eg_first.release();   // (polar_ewald_field_grid: tables, T, V)
   h->d_pr_qa.release(); h->d_pr_type.release(); h->d_pr_out.release(); h->d_pr_type_s.release(); h->pr_types_valid = false;   // (polar_probe_at: sites, results, the records' types)
+  h->d_fg_out.release();   // (polar_field_grad_at)
   if (!h->types_set || !h->coul_set) throw std::runtime_error("polar_compute before the pair tables were set: polar_pair_init (or polar_set_types), then polar_set_coul with the Coulomb tables of Pair::init_tables unless pair_modify table 0");
   if (!h->box_set || !h->atoms_set || !h->neigh_set) throw std::runtime_error("polar_compute before polar_set_box/polar_set_atoms/polar_set_neighbors");
   const polar_settings &st = h->ph.st;
@@ -1356,6 +1357,77 @@ void probe_at_pass(polar_handle *h, int m, const double *x, const int *type, con
   if (e_total) HIPCHECK(hipMemcpyAsync(e_total, out.et(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
   if (e_coul) HIPCHECK(hipMemcpyAsync(e_coul, out.ec(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
   if (e_pol) HIPCHECK(hipMemcpyAsync(e_pol, out.ep(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  float t = 0.f;
+  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
+  if (ms) *ms += (double)t;
+}
+
+// polar_field_grad_at, one pass: field_at_pass with k_field_grad_at (polar_field_grad_at.hpp) -- the same uploads, cutoffs, e2s,
+// exponential constants and box origin, the events ev_fa[0..1] -- and the block of 18 doubles per point in d_fg_out, where it
+// stays for polar_probe_force_at.  Nothing of the handle's step state is written.
+void field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *g_static,
+                        double *g_induced, double *e_static, double *e_induced, double *ms) {
+  const polar_settings &st = h->ph.st;
+  const bool ap = !(st.dd_cutoff > 0.0);
+  const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fg_out.ensure(POLAR_FIELD_GRAD_DOUBLES * mm);
+  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
+  HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
+  int *d_skip = nullptr, *d_pmol = nullptr;
+  if (skip_atom) { d_skip = h->d_fa_idx.p; HIPCHECK(hipMemcpyAsync(d_skip, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  if (molecule) { d_pmol = h->d_fa_idx.p + mm; HIPCHECK(hipMemcpyAsync(d_pmol, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  const double rc = st.cut_coul;
+  const PointCut cut{rc * rc, st.dd_cutoff * st.dd_cutoff, 1.0 / (rc * rc), 2.0 / rc, st.polar_damp};
+  const FieldGradOut out{h->d_fg_out.p};
+  const double e2s = std::sqrt(h->P.qqrd2e);
+  const ExpCoef K = make_expcoef();
+  CellGrid cg = h->grid;   // (exact mode has built no grid: the kernel takes the box origin from it in both modes)
+  for (int k = 0; k < 3; k++) cg.lo[k] = h->boxlo[k];
+  const dim3 grid(nblk(m, POLAR_ROWS_PER_BLOCK)), block(POLAR_BLOCK);
+  HIPCHECK(hipEventRecord(h->ev_fa[0], s));
+#define FG(AP, D)                                                                                                                \
+  k_field_grad_at<AP, D><<<grid, block, 0, s>>>(m, h->d_fa_x.p, d_skip, d_pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,     \
+                                                h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, cg,                 \
+                                                AP ? nullptr : h->d_cell_first.p, cut, e2s, K, out)
+  if (ap) { if (expd) FG(true, 0); else FG(true, 1); }
+  else    { if (expd) FG(false, 0); else FG(false, 1); }
+#undef FG
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa[1], s));
+  if (e_static) HIPCHECK(hipMemcpyAsync(e_static, out.es(), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (e_induced) HIPCHECK(hipMemcpyAsync(e_induced, out.ei(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (g_static) HIPCHECK(hipMemcpyAsync(g_static, out.gs(mm), 6 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (g_induced) HIPCHECK(hipMemcpyAsync(g_induced, out.gi(mm), 6 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  float t = 0.f;
+  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
+  if (ms) *ms += (double)t;
+}
+
+// polar_probe_force_at, one pass.  f_lj: a pass of polar_probe_at that asks for nothing but the LJ force (k_probe_lj's FORCE
+// instance: the bits of that call).  f_coul, f_pol: a gradient pass with no host output, which leaves the block in d_fg_out and
+// has synchronised; then k_probe_force_combine, one thread per point, behind the site's q and alpha.
+void probe_force_at_pass(polar_handle *h, int m, const double *x, const int *type, const double *q, const double *alpha,
+                         const int *skip_atom, const int *molecule, double *f_lj, double *f_coul, double *f_pol, double *ms) {
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  if (f_lj) probe_at_pass(h, m, x, type, nullptr, nullptr, skip_atom, molecule, nullptr, nullptr, nullptr, f_lj, nullptr, ms);
+  if (!f_coul && !f_pol) return;
+  field_grad_at_pass(h, m, x, skip_atom, molecule, nullptr, nullptr, nullptr, nullptr, ms);
+  h->d_pr_qa.ensure(2 * mm);
+  const double *d_q = nullptr, *d_a = nullptr;
+  if (f_coul && q) { d_q = h->d_pr_qa.p; HIPCHECK(hipMemcpyAsync(h->d_pr_qa.p, q, mm * sizeof(double), hipMemcpyHostToDevice, s)); }
+  if (f_pol && alpha) { d_a = h->d_pr_qa.p + mm; HIPCHECK(hipMemcpyAsync(h->d_pr_qa.p + mm, alpha, mm * sizeof(double), hipMemcpyHostToDevice, s)); }
+  const FieldGradOut out{h->d_fg_out.p};
+  HIPCHECK(hipEventRecord(h->ev_fa[0], s));
+  k_probe_force_combine<<<nblk(m, 256), 256, 0, s>>>(m, d_q, d_a, std::sqrt(h->P.qqrd2e), out);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa[1], s));
+  if (f_coul) HIPCHECK(hipMemcpyAsync(f_coul, out.fc(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (f_pol) HIPCHECK(hipMemcpyAsync(f_pol, out.fp(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHECK(hipStreamSynchronize(s));
   float t = 0.f;
   HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
