@@ -25,10 +25,12 @@ namespace polar {
 
 struct InputError : std::runtime_error {
   explicit InputError(const char *m) : std::runtime_error(m) {}
+  explicit InputError(const std::string &m) : std::runtime_error(m) {}
 };
 // a mode the library does not offer (POLAR_ERR_UNSUPPORTED)
 struct Unsupported : std::runtime_error {
   explicit Unsupported(const char *m) : std::runtime_error(m) {}
+  explicit Unsupported(const std::string &m) : std::runtime_error(m) {}
 };
 
 inline void settings_defaults(polar_settings &s) {  // PS.cpp:65-78

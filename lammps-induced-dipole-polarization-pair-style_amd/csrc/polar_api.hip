@@ -181,6 +181,41 @@ void upload_neighbor_rows(polar_handle *h, int inum, const int *ilist, const int
   h->device_list = false;
   h->full_list = h->user_full_list;
 }
+
+/* ---- the calls that look at a finished step from caller-supplied points -------------------------------------------- */
+// What every one of them refuses, in this order, under the entry's own name ...
+void point_call_state(polar_handle *h, const std::string &name) {
+  if (sharded(h)) throw Unsupported(name + ": not offered on a row-sharded handle");
+  if (tile_mode(h)) throw Unsupported(name + ": not offered with the tile sweep (lab build)");
+  if (!h->field_ready) throw std::runtime_error(name + ": no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
+}
+// ... and what those with a point list check after that (periodic_list: the list mode's walk needs a box periodic in every
+// direction).  Zeroes *device_ms and, on a polar_ewald handle, the split device times.  False: no points, nothing to do.
+bool point_call_begin(polar_handle *h, const std::string &name, bool periodic_list, long long npoints, const double *x,
+                      const int *skip_atom, double *device_ms) {
+  point_call_state(h, name);
+  if (periodic_list && h->ph.st.dd_cutoff > 0.0 && !(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2]))
+    throw Unsupported(name + ": list mode (dd_cutoff > 0) needs a box periodic in every direction");
+  if (npoints < 0) throw InputError(name + ": negative point count");
+  if (device_ms) *device_ms = 0.0;
+  if (ewald_on(h)) h->ew_fa_ms[0] = h->ew_fa_ms[1] = 0.0;
+  if (npoints == 0) return false;
+  if (!x) throw InputError(name + ": null pointer");
+  const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
+  check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+  return true;
+}
+// The passes of a call: pass(p0, m) for the points [p0, p0 + m).  POLAR_FIELD_AT_CHUNK is read at every call: a pass holds at
+// most that many points on the device.
+template <class F>
+void point_passes(long long npoints, F pass) {
+  const char *e = getenv("POLAR_FIELD_AT_CHUNK");
+  const long long chunk = field_at_chunk(e ? atoll(e) : 0);
+  for (long long p0 = 0; p0 < npoints; p0 += chunk) pass(p0, (int)std::min(chunk, npoints - p0));
+}
+// the part of a per-point array (w values per point) that starts at point p0; null stays null
+template <class T>
+T *from(T *a, long long p0, int w = 1) { return a ? a + w * p0 : nullptr; }
 }  // namespace
 
 
@@ -760,29 +795,13 @@ int polar_field_at(polar_handle *h, long long npoints, const double *x, const in
                    double *e_static, double *e_induced, double *phi_static, double *phi_induced, double *device_ms) {
   return guarded(h, [&]() {
     need_device(h);
-    const polar_settings &st = h->ph.st;
     if (ewald_on(h)) throw Unsupported("polar_field_at: with polar_ewald the static field is not the shifted-force one");
-    if (sharded(h)) throw Unsupported("polar_field_at: not offered on a row-sharded handle");
-    if (tile_mode(h)) throw Unsupported("polar_field_at: not offered with the tile sweep (lab build)");
-    if (!h->field_ready) throw std::runtime_error("polar_field_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
-    if (st.dd_cutoff > 0.0 && !(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2]))
-      throw Unsupported("polar_field_at: list mode (dd_cutoff > 0) needs a box periodic in every direction");
-    if (npoints < 0) throw InputError("polar_field_at: negative point count");
-    if (device_ms) *device_ms = 0.0;
-    if (npoints == 0) return (int)POLAR_OK;
-    if (!x) throw InputError("polar_field_at: null pointer");
-    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
-    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    if (!point_call_begin(h, "polar_field_at", true, npoints, x, skip_atom, device_ms)) return (int)POLAR_OK;
     HIPCHECK(hipSetDevice(h->device));
-    // read at every call: a pass holds at most this many points on the device
-    const char *e = getenv("POLAR_FIELD_AT_CHUNK");
-    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
-    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
-      const int m = (int)std::min(chunk, npoints - p0);
-      field_at_pass(h, m, x + 3 * p0, skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr,
-                    e_static ? e_static + 3 * p0 : nullptr, e_induced ? e_induced + 3 * p0 : nullptr,
-                    phi_static ? phi_static + p0 : nullptr, phi_induced ? phi_induced + p0 : nullptr, device_ms);
-    }
+    point_passes(npoints, [&](long long p0, int m) {
+      field_at_pass(h, m, x + 3 * p0, from(skip_atom, p0), from(molecule, p0), from(e_static, p0, 3), from(e_induced, p0, 3),
+                    from(phi_static, p0), from(phi_induced, p0), device_ms);
+    });
     return (int)POLAR_OK;
   });
 }
@@ -793,25 +812,12 @@ int polar_ewald_field_at(polar_handle *h, long long npoints, const double *x, co
   return guarded(h, [&]() {
     need_device(h);
     if (!ewald_on(h)) throw Unsupported("polar_ewald_field_at: the handle runs without polar_ewald; polar_field_at maps its shifted-force field");
-    if (sharded(h)) throw Unsupported("polar_ewald_field_at: not offered on a row-sharded handle");
-    if (tile_mode(h)) throw Unsupported("polar_ewald_field_at: not offered with the tile sweep (lab build)");
-    if (!h->field_ready) throw std::runtime_error("polar_ewald_field_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
-    if (npoints < 0) throw InputError("polar_ewald_field_at: negative point count");
-    if (device_ms) *device_ms = 0.0;
-    h->ew_fa_ms[0] = h->ew_fa_ms[1] = 0.0;
-    if (npoints == 0) return (int)POLAR_OK;
-    if (!x) throw InputError("polar_ewald_field_at: null pointer");
-    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
-    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    if (!point_call_begin(h, "polar_ewald_field_at", false, npoints, x, skip_atom, device_ms)) return (int)POLAR_OK;
     HIPCHECK(hipSetDevice(h->device));
-    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
-    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
-    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
-      const int m = (int)std::min(chunk, npoints - p0);
-      ewald_field_at_pass(h, m, x + 3 * p0, skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr,
-                          e_static ? e_static + 3 * p0 : nullptr, e_induced ? e_induced + 3 * p0 : nullptr,
-                          phi_static ? phi_static + p0 : nullptr, phi_induced ? phi_induced + p0 : nullptr, device_ms);
-    }
+    point_passes(npoints, [&](long long p0, int m) {
+      ewald_field_at_pass(h, m, x + 3 * p0, from(skip_atom, p0), from(molecule, p0), from(e_static, p0, 3), from(e_induced, p0, 3),
+                          from(phi_static, p0), from(phi_induced, p0), device_ms);
+    });
     return (int)POLAR_OK;
   });
 }
@@ -823,36 +829,20 @@ int polar_probe_at(polar_handle *h, long long npoints, const double *x, const in
   return guarded(h, [&]() {
     need_device(h);
     const polar_settings &st = h->ph.st;
-    const bool list = st.dd_cutoff > 0.0, lj = e_lj || f_lj, field = e_coul || e_pol || e_total;
-    if (sharded(h)) throw Unsupported("polar_probe_at: not offered on a row-sharded handle");
-    if (tile_mode(h)) throw Unsupported("polar_probe_at: not offered with the tile sweep (lab build)");
-    if (!h->field_ready) throw std::runtime_error("polar_probe_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
-    if (list && !(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2]))
-      throw Unsupported("polar_probe_at: list mode (dd_cutoff > 0) needs a box periodic in every direction");
-    if (npoints < 0) throw InputError("polar_probe_at: negative point count");
-    if (device_ms) *device_ms = 0.0;
-    if (ewald_on(h)) h->ew_fa_ms[0] = h->ew_fa_ms[1] = 0.0;
-    if (npoints == 0) return (int)POLAR_OK;
-    if (!x) throw InputError("polar_probe_at: null pointer");
-    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
-    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    const bool lj = e_lj || f_lj, field = e_coul || e_pol || e_total;
+    if (!point_call_begin(h, "polar_probe_at", true, npoints, x, skip_atom, device_ms)) return (int)POLAR_OK;
     check_probe_sites(npoints, type, h->ntypes, q, alpha, lj);
     if (lj) {
       double width[3];
       box_widths(h->box, width);
-      check_probe_reach(list, h->probe_reach_max, st.cut_coul, st.dd_cutoff, width, h->box.periodic);
+      check_probe_reach(st.dd_cutoff > 0.0, h->probe_reach_max, st.cut_coul, st.dd_cutoff, width, h->box.periodic);
     }
     if (!lj && !field) return (int)POLAR_OK;
     HIPCHECK(hipSetDevice(h->device));
-    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
-    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
-    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
-      const int m = (int)std::min(chunk, npoints - p0);
-      probe_at_pass(h, m, x + 3 * p0, type ? type + p0 : nullptr, q ? q + p0 : nullptr, alpha ? alpha + p0 : nullptr,
-                    skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr, e_lj ? e_lj + p0 : nullptr,
-                    e_coul ? e_coul + p0 : nullptr, e_pol ? e_pol + p0 : nullptr, f_lj ? f_lj + 3 * p0 : nullptr,
-                    e_total ? e_total + 3 * p0 : nullptr, device_ms);
-    }
+    point_passes(npoints, [&](long long p0, int m) {
+      probe_at_pass(h, m, x + 3 * p0, from(type, p0), from(q, p0), from(alpha, p0), from(skip_atom, p0), from(molecule, p0), from(e_lj, p0),
+                    from(e_coul, p0), from(e_pol, p0), from(f_lj, p0, 3), from(e_total, p0, 3), device_ms);
+    });
     return (int)POLAR_OK;
   });
 }
@@ -862,28 +852,13 @@ int polar_field_grad_at(polar_handle *h, long long npoints, const double *x, con
                         double *g_static, double *g_induced, double *e_static, double *e_induced, double *device_ms) {
   return guarded(h, [&]() {
     need_device(h);
-    const polar_settings &st = h->ph.st;
     if (ewald_on(h)) throw Unsupported("polar_field_grad_at: not offered with polar_ewald (the gradient of the real-space erfc part and of the reciprocal part is a follow-up)");
-    if (sharded(h)) throw Unsupported("polar_field_grad_at: not offered on a row-sharded handle");
-    if (tile_mode(h)) throw Unsupported("polar_field_grad_at: not offered with the tile sweep (lab build)");
-    if (!h->field_ready) throw std::runtime_error("polar_field_grad_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
-    if (st.dd_cutoff > 0.0 && !(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2]))
-      throw Unsupported("polar_field_grad_at: list mode (dd_cutoff > 0) needs a box periodic in every direction");
-    if (npoints < 0) throw InputError("polar_field_grad_at: negative point count");
-    if (device_ms) *device_ms = 0.0;
-    if (npoints == 0) return (int)POLAR_OK;
-    if (!x) throw InputError("polar_field_grad_at: null pointer");
-    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
-    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    if (!point_call_begin(h, "polar_field_grad_at", true, npoints, x, skip_atom, device_ms)) return (int)POLAR_OK;
     HIPCHECK(hipSetDevice(h->device));
-    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
-    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
-    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
-      const int m = (int)std::min(chunk, npoints - p0);
-      field_grad_at_pass(h, m, x + 3 * p0, skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr,
-                         g_static ? g_static + 6 * p0 : nullptr, g_induced ? g_induced + 6 * p0 : nullptr,
-                         e_static ? e_static + 3 * p0 : nullptr, e_induced ? e_induced + 3 * p0 : nullptr, device_ms);
-    }
+    point_passes(npoints, [&](long long p0, int m) {
+      field_grad_at_pass(h, m, x + 3 * p0, from(skip_atom, p0), from(molecule, p0), from(g_static, p0, 6), from(g_induced, p0, 6),
+                         from(e_static, p0, 3), from(e_induced, p0, 3), device_ms);
+    });
     return (int)POLAR_OK;
   });
 }
@@ -894,35 +869,21 @@ int polar_probe_force_at(polar_handle *h, long long npoints, const double *x, co
   return guarded(h, [&]() {
     need_device(h);
     const polar_settings &st = h->ph.st;
-    const bool list = st.dd_cutoff > 0.0, lj = f_lj != nullptr, field = f_coul || f_pol;
+    const bool lj = f_lj != nullptr, field = f_coul || f_pol;
     if (ewald_on(h)) throw Unsupported("polar_probe_force_at: not offered with polar_ewald (the gradient of the Ewald field is a follow-up)");
-    if (sharded(h)) throw Unsupported("polar_probe_force_at: not offered on a row-sharded handle");
-    if (tile_mode(h)) throw Unsupported("polar_probe_force_at: not offered with the tile sweep (lab build)");
-    if (!h->field_ready) throw std::runtime_error("polar_probe_force_at: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
-    if (list && !(h->box.periodic[0] && h->box.periodic[1] && h->box.periodic[2]))
-      throw Unsupported("polar_probe_force_at: list mode (dd_cutoff > 0) needs a box periodic in every direction");
-    if (npoints < 0) throw InputError("polar_probe_force_at: negative point count");
-    if (device_ms) *device_ms = 0.0;
-    if (npoints == 0) return (int)POLAR_OK;
-    if (!x) throw InputError("polar_probe_force_at: null pointer");
-    const double tilt[3] = {h->box.xy, h->box.xz, h->box.yz};
-    check_points(npoints, x, skip_atom, h->nlocal, h->boxlo, h->box.prd, h->box.triclinic ? tilt : nullptr, h->box.periodic);
+    if (!point_call_begin(h, "polar_probe_force_at", true, npoints, x, skip_atom, device_ms)) return (int)POLAR_OK;
     check_probe_sites(npoints, type, h->ntypes, q, alpha, lj);
     if (lj) {   // (polar_probe_at's reach check: f_lj is that call's)
       double width[3];
       box_widths(h->box, width);
-      check_probe_reach(list, h->probe_reach_max, st.cut_coul, st.dd_cutoff, width, h->box.periodic);
+      check_probe_reach(st.dd_cutoff > 0.0, h->probe_reach_max, st.cut_coul, st.dd_cutoff, width, h->box.periodic);
     }
     if (!lj && !field) return (int)POLAR_OK;
     HIPCHECK(hipSetDevice(h->device));
-    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
-    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
-    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
-      const int m = (int)std::min(chunk, npoints - p0);
-      probe_force_at_pass(h, m, x + 3 * p0, type ? type + p0 : nullptr, q ? q + p0 : nullptr, alpha ? alpha + p0 : nullptr,
-                          skip_atom ? skip_atom + p0 : nullptr, molecule ? molecule + p0 : nullptr, f_lj ? f_lj + 3 * p0 : nullptr,
-                          f_coul ? f_coul + 3 * p0 : nullptr, f_pol ? f_pol + 3 * p0 : nullptr, device_ms);
-    }
+    point_passes(npoints, [&](long long p0, int m) {
+      probe_force_at_pass(h, m, x + 3 * p0, from(type, p0), from(q, p0), from(alpha, p0), from(skip_atom, p0), from(molecule, p0),
+                          from(f_lj, p0, 3), from(f_coul, p0, 3), from(f_pol, p0, 3), device_ms);
+    });
     return (int)POLAR_OK;
   });
 }
@@ -933,9 +894,7 @@ int polar_ewald_field_grid(polar_handle *h, const int n[3], const double offset[
   return guarded(h, [&]() {
     need_device(h);
     if (!ewald_on(h)) throw Unsupported("polar_ewald_field_grid: the handle runs without polar_ewald; polar_field_at maps its shifted-force field");
-    if (sharded(h)) throw Unsupported("polar_ewald_field_grid: not offered on a row-sharded handle");
-    if (tile_mode(h)) throw Unsupported("polar_ewald_field_grid: not offered with the tile sweep (lab build)");
-    if (!h->field_ready) throw std::runtime_error("polar_ewald_field_grid: no finished step to look at (call it after polar_compute / polar_step_finish and before the next polar_set_*)");
+    point_call_state(h, "polar_ewald_field_grid");
     double off[3];
     const long long npoints = check_grid(n, offset, off);
     if (device_ms) *device_ms = 0.0;
@@ -943,14 +902,10 @@ int polar_ewald_field_grid(polar_handle *h, const int n[3], const double offset[
     HIPCHECK(hipSetDevice(h->device));
     EwGridCall call;
     ewald_field_grid_begin(h, n, off, call, device_ms);
-    const char *e = getenv("POLAR_FIELD_AT_CHUNK");   // read at every call, as polar_field_at
-    const long long chunk = field_at_chunk(e ? atoll(e) : 0);
-    for (long long p0 = 0; p0 < npoints; p0 += chunk) {
-      const int m = (int)std::min(chunk, npoints - p0);
-      ewald_field_grid_pass(h, call, p0, m, x_out ? x_out + 3 * p0 : nullptr, e_static ? e_static + 3 * p0 : nullptr,
-                            e_induced ? e_induced + 3 * p0 : nullptr, phi_static ? phi_static + p0 : nullptr,
-                            phi_induced ? phi_induced + p0 : nullptr, device_ms);
-    }
+    point_passes(npoints, [&](long long p0, int m) {
+      ewald_field_grid_pass(h, call, p0, m, from(x_out, p0, 3), from(e_static, p0, 3), from(e_induced, p0, 3), from(phi_static, p0),
+                            from(phi_induced, p0), device_ms);
+    });
     return (int)POLAR_OK;
   });
 }

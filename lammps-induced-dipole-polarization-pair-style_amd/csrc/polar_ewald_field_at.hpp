@@ -3,11 +3,11 @@
 // the hand-written HIP kernels (gfx950 / CDNA4, wave64) of the lj/cut/coul/long/polarization pair style.
 //
 // k_ew_point_real: the real-space static sums and the induced sums.  ONE WAVE PER POINT, four points per 256-thread workgroup,
-//   the closed-form wrap of the point into the box and then the walk of k_field_at (polar_field_at.hpp): every record in exact
-//   mode, the +-2 stencil runs through d_cell_first in list mode (listed once per point into LDS, so that the pair loop carries
-//   no stencil state: erfc and erf take the registers); lanes stride the records, eight wave_sums, lane 0 stores, no
-//   atomics.  The walk is written a second time here (ew_point_walk): k_field_at's eight instances keep their code and their
-//   register budget.  It runs twice per point, once for the induced sums and once for the static ones.
+//   the closed-form wrap of the point into the box and then the walk of k_field_at (both polar_point_walk.hpp's): every record in
+//   exact mode; in list mode the runs of the +-2 stencil through d_cell_first are listed once per point into LDS and walked from
+//   there (ew_point_walk), so that the pair loop carries no stencil state: erfc and erf take the registers.  Lanes stride
+//   the records, eight wave_sums, lane 0 stores, no atomics.  The walk runs twice per point, once for the induced sums and once
+//   for the static ones.
 // k_ew_point_recip: the reciprocal sums.  One thread per point, 256 per workgroup; blockIdx.y indexes a chunk of (h, k) rows of
 //   the step's own k-vector table (ew_point_rows_per_chunk: a function of the table alone), so that a few hundred points still
 //   fill the machine.  kv, S and rows are wave-uniform loads out of L2; per (point, k) one complex multiply and the four sums.
@@ -20,9 +20,9 @@
 #include "polar_common.hpp"
 #include "polar_ewald.hpp"         // EwCell, ew_frac
 #include "polar_ewald_point.hpp"
-#include "polar_field_at.hpp"      // FieldAtOut, in_vgpr
+#include "polar_field_at.hpp"      // FieldAtOut
+#include "polar_point_walk.hpp"    // in_vgpr, point_wrap, stencil_axis, seam_part, point_walk_all
 #include "polar_rows.hpp"          // PairMath
-#include "polar_lists.hpp"         // CellGrid, cell_of
 
 namespace polar {
 
@@ -41,28 +41,13 @@ struct EwRecipMath {   // (the reciprocal sums need the phases only)
   __device__ __forceinline__ void sincospi(double x, double *s, double *c) const { ::sincospi(x, s, c); }
 };
 
-// into the box: n lattice vectors c, b, a off, each product and difference in one rounding (as k_field_at)
-__device__ __forceinline__ void ew_point_wrap(const Box &box, const double lo[3], double &px, double &py, double &pz) {
-  double fr[3];
-  frac_coords(box, lo, px, py, pz, fr);
-  const double n2 = box.periodic[2] ? floor(fr[2]) : 0.0, n1 = box.periodic[1] ? floor(fr[1]) : 0.0, n0 = box.periodic[0] ? floor(fr[0]) : 0.0;
-  pz = fma(-n2, box.prd[2], pz);
-  py = fma(-n1, box.prd[1], fma(-n2, box.yz, py));
-  px = fma(-n0, box.prd[0], fma(-n1, box.xy, fma(-n2, box.xz, px)));
-}
-
 // The walk of one point's candidate records, lanes striding them: every record with Domain::closest_image's image (exact mode),
 // or the runs of consecutive records listed in `runs` with the list mode's rounded image.  f(j, record, dx, dy, dz) per candidate.
 template <bool ALLPAIRS, class F>
 __device__ __forceinline__ void ew_point_walk(int lane, int nlocal, const AtomRec *__restrict__ rec, const Box &box, double px, double py,
                                               double pz, const int *runs, int nruns, F f) {
   if (ALLPAIRS) {
-    for (int j = lane; j < nlocal; j += 64) {
-      const AtomRec rj = rec[j];
-      double dx, dy, dz;
-      min_image_del(box, px, py, pz, rj.x, rj.y, rj.z, dx, dy, dz);
-      f(j, rj, dx, dy, dz);
-    }
+    point_walk_all(lane, nlocal, rec, box, px, py, pz, f);
   } else {
     for (int r = 0; r < nruns; r++) {
       const int beg = __builtin_amdgcn_readfirstlane(runs[2 * r]), end = __builtin_amdgcn_readfirstlane(runs[2 * r + 1]);
@@ -102,7 +87,7 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_ew_point_real(int npts, 
   if (!ALLPAIRS && DAMP == 0) { Kp.log2e = in_vgpr(K.log2e); Kp.ln2hi = in_vgpr(K.ln2hi); Kp.ln2lo = in_vgpr(K.ln2lo); }   // (as k_field_at)
   const EwPointMath pmath{Kp};
   PointSums s = {0, 0, 0, 0, 0, 0, 0, 0};
-  ew_point_wrap(box, g.lo, px, py, pz);
+  point_wrap(box, g.lo, px, py, pz);
   // the box of the pair loops: list mode's is periodic in every direction (polar_ewald steps run in no other box) and sits in
   // vector registers
   Box pbox = box;
@@ -121,21 +106,17 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_ew_point_real(int npts, 
     // the stencil one run of cells along x, two where it crosses the periodic seam; an axis with fewer than five cells is
     // walked once, cells 0 .. nc-1 -- so that the pair loops, whose erfc / erf need the scalar registers, carry no stencil state.
     const int nc0 = g.nc[0], nc1 = g.nc[1], nc2 = g.nc[2];
-    const int c0 = c % nc0, c1 = (c / nc0) % nc1, c2 = c / (nc0 * nc1);
-    const int n0 = nc0 < 5 ? nc0 : 5, n1 = nc1 < 5 ? nc1 : 5, n2 = nc2 < 5 ? nc2 : 5;
-    int x0 = nc0 < 5 ? 0 : c0 - 2, y0 = nc1 < 5 ? 0 : c1 - 2, z0 = nc2 < 5 ? 0 : c2 - 2;
-    x0 += x0 < 0 ? nc0 : 0; y0 += y0 < 0 ? nc1 : 0; z0 += z0 < 0 ? nc2 : 0;   // first cell per axis, in [0, nc)
-    const int lenA = n0 < nc0 - x0 ? n0 : nc0 - x0;          // cells up to the seam; the other n0 - lenA start at cell 0
-    nruns = 2 * n1 * n2;                                       // <= 50
+    const ProbeAxis a0 = stencil_axis(c % nc0, nc0), a1 = stencil_axis((c / nc0) % nc1, nc1), a2 = stencil_axis(c / (nc0 * nc1), nc2);
+    nruns = 2 * a1.count * a2.count;                           // <= 50
     if (lane < nruns) {
-      const int part = lane & 1, o1 = (lane >> 1) % n1, o2 = (lane >> 1) / n1;
-      int z = z0 + o2, y = y0 + o1;
+      const int o1 = (lane >> 1) % a1.count, o2 = (lane >> 1) / a1.count;
+      int z = a2.first + o2, y = a1.first + o1;
       z -= z >= nc2 ? nc2 : 0;
       y -= y >= nc1 ? nc1 : 0;
       const long long base = ((long long)z * nc1 + y) * nc0;
-      const int first = part ? 0 : x0, len = part ? n0 - lenA : lenA;
-      runs[2 * lane] = len > 0 ? (int)cell_first[base + first] : 0;
-      runs[2 * lane + 1] = len > 0 ? (int)cell_first[base + first + len] : 0;
+      const ProbeAxis run = seam_part(a0, nc0, lane & 1);
+      runs[2 * lane] = run.count > 0 ? (int)cell_first[base + run.first] : 0;
+      runs[2 * lane + 1] = run.count > 0 ? (int)cell_first[base + run.first + run.count] : 0;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -173,7 +154,7 @@ static __global__ __launch_bounds__(256) void k_ew_point_recip(int np, int p0, c
   const size_t p = (size_t)p0 + t;
   double px = xp[3 * p], py = xp[3 * p + 1], pz = xp[3 * p + 2];
   const double lo[3] = {lo0, lo1, lo2};
-  ew_point_wrap(box, lo, px, py, pz);
+  point_wrap(box, lo, px, py, pz);
   double sx, sy, sz;
   ew_frac(cell, px, py, pz, sx, sy, sz);
   const int r0 = blockIdx.y * rows_per_chunk, r1 = min(nrow, r0 + rows_per_chunk);

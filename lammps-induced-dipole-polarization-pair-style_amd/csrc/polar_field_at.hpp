@@ -6,22 +6,14 @@
 // handed over with x running fastest: neighbouring points re-read the same records out of L1 / L2).  The lanes stride the
 // candidate atoms, the eight sums are reduced with wave_sum, lane 0 stores: no atomics, and a point's result depends on
 // nothing but the point and the records -- not on the pass it ran in, nor on what else the call holds.
-//   ALLPAIRS (exact mode): every record 0 .. nlocal-1, image by min_image_del (closest_image), as k_static_field<true>.
-//   Before either, whole lattice vectors come off the point along the periodic directions, once and in closed form (floor of
-//   the fractional coordinates, as k_pack wraps an atom; the host has refused points further than 2^30 box lengths out):
-//   closest_image's add / subtract loops then see an in-box point, as they do for an atom, however far out the caller's was.
-//   list mode: the point's cell is cell_of's, and the records of the +-2 stencil of the list grid are walked through d_cell_first: list_grid
-//   (polar_plan.hpp) makes a cell at least cutall / 2 high, so +-2 cells cover the cutoff sphere of any point of the centre
-//   cell.  Image by min_image_rint.  Along x the stencil's cells are consecutive cells, i.e. ONE run of consecutive records
-//   (two where it crosses the periodic seam): empty cells cost nothing, short cells share a trip.  An axis with fewer than
-//   five cells (a periodic one has at least four) is walked once, cells 0 .. nc-1: the 5-cell stencil would meet a cell twice.
-//   Every axis must be periodic (the host refuses other boxes).
+// The wrap of the point into the box and the two walks -- every record in exact mode (ALLPAIRS), the +-2 stencil of the point's
+// cell in list mode -- are polar_point_walk.hpp's, described there.
 #pragma once
 
 #include "polar_common.hpp"
 #include "polar_point_pair.hpp"
 #include "polar_rows.hpp"    // PairMath
-#include "polar_lists.hpp"   // CellGrid, cell_of
+#include "polar_point_walk.hpp"   // in_vgpr, point_wrap, point_walk_all, point_walk_cells
 
 namespace polar {
 
@@ -34,14 +26,6 @@ struct FieldAtOut {
   __host__ __device__ double *ps(size_t npts) const { return base + 6 * npts; }
   __host__ __device__ double *pi(size_t npts) const { return base + 7 * npts; }
 };
-
-// A wave-uniform value parked in a VECTOR register.  The list-mode instances hold the box, the exponential's constants, the
-// stencil's loop state and the table pointers in scalar registers -- more than the 102 a wave has: the point, the cutoffs,
-// e2s and the list mode's box, read once per pair or once per point, go to the vector file, which has room (no scalar register is spilled).
-__device__ __forceinline__ double in_vgpr(double v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
 
 template <bool ALLPAIRS, int DAMP, bool PHI>
 static __global__ __launch_bounds__(POLAR_BLOCK) void k_field_at(int npts, const double *__restrict__ xp, const int *__restrict__ skip_atom,
@@ -64,22 +48,13 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_field_at(int npts, const
   if (!ALLPAIRS && DAMP == 0) { Kp.log2e = in_vgpr(K.log2e); Kp.ln2hi = in_vgpr(K.ln2hi); Kp.ln2lo = in_vgpr(K.ln2lo); }   // (the last scalar registers over budget)
   const PairMath pmath{Kp, 0.0};
   PointSums s = {0, 0, 0, 0, 0, 0, 0, 0};
-  {   // into the box: n lattice vectors c, b, a off, each product and difference in one rounding
-    double fr[3];
-    frac_coords(box, g.lo, px, py, pz, fr);
-    const double n2 = box.periodic[2] ? floor(fr[2]) : 0.0, n1 = box.periodic[1] ? floor(fr[1]) : 0.0, n0 = box.periodic[0] ? floor(fr[0]) : 0.0;
-    pz = fma(-n2, box.prd[2], pz);
-    py = fma(-n1, box.prd[1], fma(-n2, box.yz, py));
-    px = fma(-n0, box.prd[0], fma(-n1, box.xy, fma(-n2, box.xz, px)));
-  }
+  point_wrap(box, g.lo, px, py, pz);
+  const auto pair = [&](int j, const AtomRec &rj, double dx, double dy, double dz) {
+    const bool molok = pm == 0 || pm != mol_s[j];
+    if (j != sk) polar_point_pair<ALLPAIRS, DAMP, PHI>(pmath, dx, dy, dz, rj.q, rj.mx, rj.my, rj.mz, rj.a, molok, cut, s);
+  };
   if (ALLPAIRS) {
-    for (int j = lane; j < nlocal; j += 64) {
-      const AtomRec rj = rec[j];
-      double dx, dy, dz;
-      min_image_del(box, px, py, pz, rj.x, rj.y, rj.z, dx, dy, dz);
-      const bool molok = pm == 0 || pm != mol_s[j];
-      if (j != sk) polar_point_pair<true, DAMP, PHI>(pmath, dx, dy, dz, rj.q, rj.mx, rj.my, rj.mz, rj.a, molok, cut, s);
-    }
+    point_walk_all(lane, nlocal, rec, box, px, py, pz, pair);
   } else {
     const int c = __builtin_amdgcn_readfirstlane(cell_of(g, box, px, py, pz));
     // the box of the pair loop: every direction is periodic here, which min_image_rint then knows at compile time; the damped
@@ -92,33 +67,8 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_field_at(int npts, const
     }
     if (DAMP == 0) { pbox.xy = in_vgpr(box.xy); pbox.xz = in_vgpr(box.xz); pbox.yz = in_vgpr(box.yz); }
     const int nc0 = g.nc[0], nc1 = g.nc[1], nc2 = g.nc[2];
-    const int c0 = c % nc0, c1 = (c / nc0) % nc1, c2 = c / (nc0 * nc1);
-    // per axis: the cells start, start + 1, ... (count of them), wrapped; fewer than five cells: all of them, once
-    const int n0 = nc0 < 5 ? nc0 : 5, n1 = nc1 < 5 ? nc1 : 5, n2 = nc2 < 5 ? nc2 : 5;
-    int x0 = nc0 < 5 ? 0 : c0 - 2, y0 = nc1 < 5 ? 0 : c1 - 2, z0 = nc2 < 5 ? 0 : c2 - 2;
-    x0 += x0 < 0 ? nc0 : 0; y0 += y0 < 0 ? nc1 : 0; z0 += z0 < 0 ? nc2 : 0;   // first cell per axis, in [0, nc)
-    const int lenA = n0 < nc0 - x0 ? n0 : nc0 - x0;          // cells up to the seam; the other n0 - lenA start at cell 0
-    for (int o2 = 0; o2 < n2; o2++) {
-      int z = z0 + o2;
-      z -= z >= nc2 ? nc2 : 0;
-      for (int o1 = 0; o1 < n1; o1++) {
-        int y = y0 + o1;
-        y -= y >= nc1 ? nc1 : 0;
-        const long long base = ((long long)z * nc1 + y) * nc0;
-        for (int part = 0; part < 2; part++) {
-          const int first = part ? 0 : x0, len = part ? n0 - lenA : lenA;
-          if (len <= 0) continue;   // (wave-uniform)
-          const int beg = (int)cell_first[base + first], end = (int)cell_first[base + first + len];
-          for (int j = beg + lane; j < end; j += 64) {
-            const AtomRec rj = rec[j];
-            double dx, dy, dz;
-            min_image_rint(pbox, px, py, pz, rj.x, rj.y, rj.z, dx, dy, dz);
-            const bool molok = pm == 0 || pm != mol_s[j];
-            if (j != sk) polar_point_pair<false, DAMP, PHI>(pmath, dx, dy, dz, rj.q, rj.mx, rj.my, rj.mz, rj.a, molok, cut, s);
-          }
-        }
-      }
-    }
+    point_walk_cells(lane, rec, pbox, g, cell_first, stencil_axis(c % nc0, nc0), stencil_axis((c / nc0) % nc1, nc1),
+                     stencil_axis(c / (nc0 * nc1), nc2), px, py, pz, pair);
   }
   s.esx = wave_sum(s.esx); s.esy = wave_sum(s.esy); s.esz = wave_sum(s.esz);
   s.eix = wave_sum(s.eix); s.eiy = wave_sum(s.eiy); s.eiz = wave_sum(s.eiz);

@@ -4,13 +4,10 @@
 // hand-written HIP kernels (gfx950 / CDNA4, wave64) of the lj/cut/coul/long/polarization pair style; see polar_kernels.hpp for
 // the mapping and the index spaces.
 //
-// k_field_grad_at has the mapping and the walk of k_field_at (polar_field_at.hpp), restated here so that k_field_at's eight
-// instances keep their code and their register counts: ONE WAVE PER POINT, four consecutive points per 256-thread workgroup, the
-// closed-form wrap of the point into the box, then
-//   ALLPAIRS (exact mode): every record 0 .. nlocal-1, image by min_image_del;
-//   list mode: the +-2 stencil of the point's cell through d_cell_first, per (z, y) one run of consecutive records along x (two
-//   across the periodic seam), an axis with fewer than five cells walked once; image by min_image_rint, every direction periodic
-//   (the host refuses other boxes).
+// k_field_grad_at has the mapping and the walk of k_field_at (polar_field_at.hpp), both polar_point_walk.hpp's: ONE WAVE PER
+// POINT, the closed-form wrap of the point into the box, then every record (ALLPAIRS, exact mode) or the +-2 stencil of the
+// point's cell (list mode).  The wrap and the exact-mode walk are called from there; the list-mode loops are point_walk_cells'
+// written out in the kernel, because the damped instance is slower through the shared ones.
 // The lanes stride the candidate records in k_field_at's order, the 18 sums (6 of the field, 12 of the gradient) are reduced with
 // wave_sum, lane 0 stores: no atomics, no LDS, and a point's bits depend on the point and the records alone.  The six field sums
 // are formed by k_field_at's expressions in k_field_at's order: they have its bits.
@@ -19,10 +16,9 @@
 #pragma once
 
 #include "polar_common.hpp"
-#include "polar_field_at.hpp"    // in_vgpr
 #include "polar_point_grad_pair.hpp"
 #include "polar_rows.hpp"    // PairMath
-#include "polar_lists.hpp"   // CellGrid, cell_of
+#include "polar_point_walk.hpp"   // in_vgpr, point_wrap, point_walk_all
 
 namespace polar {
 
@@ -65,22 +61,13 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_field_grad_at(int npts, 
   if (!ALLPAIRS && DAMP == 0) { Kp.log2e = in_vgpr(K.log2e); Kp.ln2hi = in_vgpr(K.ln2hi); Kp.ln2lo = in_vgpr(K.ln2lo); }   // (as k_field_at)
   const PairMath pmath{Kp, 0.0};
   PointGradSums s = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}};
-  {   // into the box: n lattice vectors c, b, a off, each product and difference in one rounding (as k_field_at)
-    double fr[3];
-    frac_coords(box, g.lo, px, py, pz, fr);
-    const double n2 = box.periodic[2] ? floor(fr[2]) : 0.0, n1 = box.periodic[1] ? floor(fr[1]) : 0.0, n0 = box.periodic[0] ? floor(fr[0]) : 0.0;
-    pz = fma(-n2, box.prd[2], pz);
-    py = fma(-n1, box.prd[1], fma(-n2, box.yz, py));
-    px = fma(-n0, box.prd[0], fma(-n1, box.xy, fma(-n2, box.xz, px)));
-  }
+  point_wrap(box, g.lo, px, py, pz);
+  const auto pair = [&](int j, const AtomRec &rj, double dx, double dy, double dz) {
+    const bool molok = pm == 0 || pm != mol[j];
+    if (j != sk) polar_point_grad_pair<ALLPAIRS, DAMP>(pmath, dx, dy, dz, rj.q, rj.mx, rj.my, rj.mz, rj.a, molok, cut, s);
+  };
   if (ALLPAIRS) {
-    for (int j = lane; j < nlocal; j += 64) {
-      const AtomRec rj = rec[j];
-      double dx, dy, dz;
-      min_image_del(box, px, py, pz, rj.x, rj.y, rj.z, dx, dy, dz);
-      const bool molok = pm == 0 || pm != mol[j];
-      if (j != sk) polar_point_grad_pair<true, DAMP>(pmath, dx, dy, dz, rj.q, rj.mx, rj.my, rj.mz, rj.a, molok, cut, s);
-    }
+    point_walk_all(lane, nlocal, rec, box, px, py, pz, pair);
   } else {
     const int c = __builtin_amdgcn_readfirstlane(cell_of(g, box, px, py, pz));
     // the box of the pair loop: every direction is periodic here, which min_image_rint then knows at compile time; the damped
@@ -92,9 +79,11 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_field_grad_at(int npts, 
       if (DAMP == 0) { pbox.prd[k] = in_vgpr(box.prd[k]); pbox.inv[k] = in_vgpr(box.inv[k]); }
     }
     if (DAMP == 0) { pbox.xy = in_vgpr(box.xy); pbox.xz = in_vgpr(box.xz); pbox.yz = in_vgpr(box.yz); }
+    // point_walk_cells with stencil_axis on every axis, written out: through the shared loops the damped instance comes out
+    // with other code (one copy of the pair body, or two in another order) and measurably slower, see DESIGN section 6h.  Any
+    // change to point_walk_cells is made here too.
     const int nc0 = g.nc[0], nc1 = g.nc[1], nc2 = g.nc[2];
     const int c0 = c % nc0, c1 = (c / nc0) % nc1, c2 = c / (nc0 * nc1);
-    // per axis: the cells start, start + 1, ... (count of them), wrapped; fewer than five cells: all of them, once
     const int n0 = nc0 < 5 ? nc0 : 5, n1 = nc1 < 5 ? nc1 : 5, n2 = nc2 < 5 ? nc2 : 5;
     int x0 = nc0 < 5 ? 0 : c0 - 2, y0 = nc1 < 5 ? 0 : c1 - 2, z0 = nc2 < 5 ? 0 : c2 - 2;
     x0 += x0 < 0 ? nc0 : 0; y0 += y0 < 0 ? nc1 : 0; z0 += z0 < 0 ? nc2 : 0;   // first cell per axis, in [0, nc)

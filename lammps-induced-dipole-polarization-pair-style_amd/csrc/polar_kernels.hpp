@@ -27,6 +27,8 @@
 // polar_ewald_field_at.hpp (`polar_ewald_field_at`: the same map for `polar_ewald` handles, real-space and reciprocal sums;
 // arithmetic in the plain-C++ polar_ewald_point.hpp) and polar_ewald_field_grid.hpp (`polar_ewald_field_grid`: that map on a
 // regular grid of the cell, the reciprocal sums as three 1-D transforms; arithmetic in the plain-C++ polar_ewald_grid.hpp).
+// The point kernels of these and of polar_probe_at.hpp / polar_field_grad_at.hpp find a point's candidate records by ONE walk,
+// polar_point_walk.hpp (the wrap into the box, every record in exact mode, a cell stencil in list mode).
 #pragma once
 
 #include "polar_common.hpp"

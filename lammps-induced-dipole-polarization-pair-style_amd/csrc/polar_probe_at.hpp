@@ -6,13 +6,11 @@
 // k_probe_lj has the mapping of k_field_at (polar_field_at.hpp), so the same caches serve a grid: ONE WAVE PER POINT, four
 // consecutive points per 256-thread workgroup, the lanes stride the candidate records, the one sum (four with FORCE) is reduced
 // with wave_sum, lane 0 stores: no atomics, no LDS, and a point's bits depend on the point, the records and the table alone.
-//   ALLPAIRS (exact mode): every record 0 .. nlocal-1 with min_image_del, after the closed-form wrap of k_field_at.
-//   list mode: the trimmed stencil of the wrapped point (probe_axis, polar_probe_plan.hpp) through d_cell_first: per axis the
-//   cells a sphere of the probe type's reach touches -- cut_lj is often a fraction of cutall, and the +-2 stencil of k_field_at
-//   would walk 125 cells for the partners of one or two.  Along x a row of the stencil is one run of consecutive records (two
-//   across the seam).  Every run is walked in the front copy of the grid first; then, where the cell order is split
-//   (polar_handle::cell_split), the same runs in the inert copy at ncell + c: the LJ sum covers ALL atoms, the inert ones
-//   included.  Image by min_image_rint, every direction periodic (the host refuses other boxes).
+// The wrap and the walks are polar_point_walk.hpp's: every record in exact mode (ALLPAIRS); in list mode the TRIMMED stencil of
+// the wrapped point (probe_axis, polar_probe_plan.hpp): per axis the cells a sphere of the probe type's reach touches -- cut_lj
+// is often a fraction of cutall, and the +-2 stencil of k_field_at would walk 125 cells for the partners of one or two.  Every
+// run is walked in the front copy of the grid first; then, where the cell order is split (polar_handle::cell_split), the same
+// runs in the inert copy at ncell + c: the LJ sum covers ALL atoms, the inert ones included.
 // The probe's row of the packed table and its reach are wave-uniform (scalar registers); the partner's entry is a
 // lane-divergent read of a table of a few hundred bytes.  A record's type comes from a table in record order (k_probe_types,
 // made once per call window).
@@ -21,8 +19,8 @@
 #pragma once
 
 #include "polar_common.hpp"
-#include "polar_field_at.hpp"    // FieldAtOut, in_vgpr
-#include "polar_lists.hpp"       // CellGrid
+#include "polar_field_at.hpp"    // FieldAtOut
+#include "polar_point_walk.hpp"  // point_wrap, point_walk_all, point_walk_cells
 #include "polar_probe_pair.hpp"
 #include "polar_probe_plan.hpp"
 
@@ -95,22 +93,15 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_probe_lj(int npts, const
   const double *__restrict__ row = ljpack + (size_t)POLAR_LJ_ENTRY * tp * (ntypes + 1);
   const CellGrid &g = pg.g;
   ProbeSums s = {0, 0, 0, 0};
-  {   // into the box: n lattice vectors c, b, a off, each product and difference in one rounding (as k_field_at)
-    double fr[3];
-    frac_coords(box, g.lo, px, py, pz, fr);
-    const double n2 = box.periodic[2] ? floor(fr[2]) : 0.0, n1 = box.periodic[1] ? floor(fr[1]) : 0.0, n0 = box.periodic[0] ? floor(fr[0]) : 0.0;
-    pz = fma(-n2, box.prd[2], pz);
-    py = fma(-n1, box.prd[1], fma(-n2, box.yz, py));
-    px = fma(-n0, box.prd[0], fma(-n1, box.xy, fma(-n2, box.xz, px)));
-  }
+  point_wrap(box, g.lo, px, py, pz);
+  // (the LJ pair needs the record's position alone, which the walk has read: the record itself is not looked at, and the walk's
+  // loads of its other fields are dead code -- the resource remarks are those of a loop that reads x, y and z through a pointer)
+  const auto pair = [&](int j, const AtomRec &, double dx, double dy, double dz) {
+    const bool molok = pm == 0 || pm != mol_s[j];
+    if (j != sk && molok) polar_probe_pair<FORCE>(dx, dy, dz, type_s[j], row, s);
+  };
   if (ALLPAIRS) {
-    for (int j = lane; j < nlocal; j += 64) {
-      const AtomRec *rj = rec + j;
-      double dx, dy, dz;
-      min_image_del(box, px, py, pz, rj->x, rj->y, rj->z, dx, dy, dz);
-      const bool molok = pm == 0 || pm != mol_s[j];
-      if (j != sk && molok) polar_probe_pair<FORCE>(dx, dy, dz, type_s[j], row, s);
-    }
+    point_walk_all(lane, nlocal, rec, box, px, py, pz, pair);
   } else {
     Box pbox = box;   // every direction is periodic here, which min_image_rint then knows at compile time
 #pragma unroll
@@ -118,37 +109,12 @@ static __global__ __launch_bounds__(POLAR_BLOCK) void k_probe_lj(int npts, const
     const double rho = wave_uniform(reach[tp]);
     double fr[3];
     frac_coords(box, g.lo, px, py, pz, fr);
-    const int nc0 = g.nc[0], nc1 = g.nc[1], nc2 = g.nc[2];
-    const ProbeAxis a0 = probe_axis(wave_uniform(fr[0]), rho * pg.dscale[0], nc0);
-    const ProbeAxis a1 = probe_axis(wave_uniform(fr[1]), rho * pg.dscale[1], nc1);
-    const ProbeAxis a2 = probe_axis(wave_uniform(fr[2]), rho * pg.dscale[2], nc2);
-    const int x0 = a0.first, n0 = a0.count;
-    const int lenA = n0 < nc0 - x0 ? n0 : nc0 - x0;          // cells up to the seam; the other n0 - lenA start at cell 0
+    const ProbeAxis a0 = probe_axis(wave_uniform(fr[0]), rho * pg.dscale[0], g.nc[0]);
+    const ProbeAxis a1 = probe_axis(wave_uniform(fr[1]), rho * pg.dscale[1], g.nc[1]);
+    const ProbeAxis a2 = probe_axis(wave_uniform(fr[2]), rho * pg.dscale[2], g.nc[2]);
     const int ncopy = pg.ncell_inert > 0 ? 2 : 1;
-    for (int copy = 0; copy < ncopy; copy++) {
-      const long long *__restrict__ cf = cell_first + (copy ? pg.ncell_inert : 0);
-      for (int o2 = 0; o2 < a2.count; o2++) {
-        int z = a2.first + o2;
-        z -= z >= nc2 ? nc2 : 0;
-        for (int o1 = 0; o1 < a1.count; o1++) {
-          int y = a1.first + o1;
-          y -= y >= nc1 ? nc1 : 0;
-          const long long base = ((long long)z * nc1 + y) * nc0;
-          for (int part = 0; part < 2; part++) {
-            const int first = part ? 0 : x0, len = part ? n0 - lenA : lenA;
-            if (len <= 0) continue;   // (wave-uniform)
-            const int beg = (int)cf[base + first], end = (int)cf[base + first + len];
-            for (int j = beg + lane; j < end; j += 64) {
-              const AtomRec *rj = rec + j;
-              double dx, dy, dz;
-              min_image_rint(pbox, px, py, pz, rj->x, rj->y, rj->z, dx, dy, dz);
-              const bool molok = pm == 0 || pm != mol_s[j];
-              if (j != sk && molok) polar_probe_pair<FORCE>(dx, dy, dz, type_s[j], row, s);
-            }
-          }
-        }
-      }
-    }
+    for (int copy = 0; copy < ncopy; copy++)   // the front copy of the grid, then the inert one
+      point_walk_cells(lane, rec, pbox, g, cell_first + (copy ? pg.ncell_inert : 0), a0, a1, a2, px, py, pz, pair);
   }
   s.e = wave_sum(s.e);
   if (FORCE) { s.fx = wave_sum(s.fx); s.fy = wave_sum(s.fy); s.fz = wave_sum(s.fz); }

@@ -89,6 +89,20 @@ POLAR_PLAN_FN ProbeAxis probe_axis(double s, double dfrac, int nc) {
   first += first < 0 ? nc : 0;
   return ProbeAxis{first, (int)(hi - lo) + 1};
 }
+// The untrimmed rule of every other point kernel (polar_point_walk.hpp): the five cells c - 2 .. c + 2 around the point's own
+// cell c, the first wrapped into [0, nc); an axis with fewer than five cells (a periodic one has at least four): all of them,
+// once -- the 5-cell stencil would meet a cell twice.
+POLAR_PLAN_FN ProbeAxis stencil_axis(int c, int nc) {
+  int first = nc < 5 ? 0 : c - 2;
+  first += first < 0 ? nc : 0;
+  return ProbeAxis{first, nc < 5 ? nc : 5};
+}
+// An axis range split at the periodic seam: part 0 = the cells from a.first up to the seam, part 1 = the rest, which start at
+// cell 0 (count 0: the range does not cross).  Along x a part is one run of consecutive cells, hence of consecutive records.
+POLAR_PLAN_FN ProbeAxis seam_part(ProbeAxis a, int nc, int part) {
+  const int len_a = a.count < nc - a.first ? a.count : nc - a.first;
+  return part ? ProbeAxis{0, a.count - len_a} : ProbeAxis{a.first, len_a};
+}
 // dfrac of the three axes from a reach and the perpendicular widths
 POLAR_PLAN_FN void probe_dfrac_scale(const double width[3], double scale[3]) {
   for (int k = 0; k < 3; k++) scale[k] = (1.0 + 1e-9) / width[k];

@@ -1158,6 +1158,63 @@ void step_begin_finish(polar_handle *h) {
   h->in_step = true;
 }
 
+// ---- what the passes of the point calls share ------------------------------------------------------------------------------
+// The points of a pass go up into d_fa_x, skip_atom and molecule (either may be null) into the halves of d_fa_idx; the event
+// pair of the passes exists from here on.  Returns where the two index arrays went (null: not given).
+struct PointIdx { int *skip, *pmol; };
+static PointIdx point_upload(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule) {
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm);
+  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
+  HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
+  PointIdx idx{nullptr, nullptr};
+  if (skip_atom) { idx.skip = h->d_fa_idx.p; HIPCHECK(hipMemcpyAsync(idx.skip, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  if (molecule) { idx.pmol = h->d_fa_idx.p + mm; HIPCHECK(hipMemcpyAsync(idx.pmol, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
+  return idx;
+}
+
+// The list grid with the box origin in it (exact mode has built no grid: the point kernels take the origin from it in both
+// modes) ...
+static CellGrid point_grid(const polar_handle *h) {
+  CellGrid cg = h->grid;
+  for (int k = 0; k < 3; k++) cg.lo[k] = h->boxlo[k];
+  return cg;
+}
+// ... and with it the other by-value arguments of the field kernels: the cutoffs, e2s, the exponential's constants.
+struct PointParm { PointCut cut; double e2s; ExpCoef K; CellGrid cg; };
+static PointParm point_parm(const polar_handle *h) {
+  const polar_settings &st = h->ph.st;
+  const double rc = st.cut_coul;
+  return PointParm{PointCut{rc * rc, st.dd_cutoff * st.dd_cutoff, 1.0 / (rc * rc), 2.0 / rc, st.polar_damp}, std::sqrt(h->P.qqrd2e), make_expcoef(),
+                   point_grid(h)};
+}
+
+// The end of a pass: the results the caller asked for come back (a null host pointer: not asked for), the stream is waited
+// for, and the device time between ev_fa[0] and ev_fa[1] is added to *ms -- with `ewald` also that between ev_fa[1] and
+// ev_fa_k, and both to the handle's ew_fa_ms.
+struct PointBack { double *host; const double *dev; size_t count; };
+static void point_finish(polar_handle *h, std::initializer_list<PointBack> back, bool ewald, double *ms) {
+  hipStream_t s = h->stream;
+  for (const PointBack &b : back)
+    if (b.host) HIPCHECK(hipMemcpyAsync(b.host, b.dev, b.count * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipStreamSynchronize(s));
+  float t = 0.f, tk = 0.f;
+  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
+  if (ewald) {
+    HIPCHECK(hipEventElapsedTime(&tk, h->ev_fa[1], h->ev_fa_k));
+    h->ew_fa_ms[0] += (double)t; h->ew_fa_ms[1] += (double)tk;
+  }
+  if (ms) *ms += ewald ? (double)t + (double)tk : (double)t;
+}
+// ... of a pass whose results are the field block in d_fa_out
+static void field_out_finish(polar_handle *h, int m, double *e_static, double *e_induced, double *phi_static, double *phi_induced, bool ewald,
+                             double *ms) {
+  const size_t mm = (size_t)m;
+  const FieldAtOut out{h->d_fa_out.p};
+  point_finish(h, {{e_static, out.es(), 3 * mm}, {e_induced, out.ei(mm), 3 * mm}, {phi_static, out.ps(mm), mm}, {phi_induced, out.pi(mm), mm}}, ewald, ms);
+}
+
 // polar_field_at, one pass: the points go up, one launch of k_field_at (polar_field_at.hpp) on the handle's stream reads the
 // records, the molecule ids and -- list mode -- the cell table the finished step left, the results the caller asked for come
 // back.  Nothing of the handle's step state is written.
@@ -1168,27 +1225,16 @@ void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom
   const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
   const bool phi = phi_static || phi_induced || phi_on_device;
   hipStream_t s = h->stream;
-  const size_t mm = (size_t)m;
-  h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fa_out.ensure(8 * mm);
-  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
-  HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
-  int *d_skip = nullptr, *d_pmol = nullptr;
-  if (skip_atom) { d_skip = h->d_fa_idx.p; HIPCHECK(hipMemcpyAsync(d_skip, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
-  if (molecule) { d_pmol = h->d_fa_idx.p + mm; HIPCHECK(hipMemcpyAsync(d_pmol, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
-  const double rc = st.cut_coul;
-  const PointCut cut{rc * rc, st.dd_cutoff * st.dd_cutoff, 1.0 / (rc * rc), 2.0 / rc, st.polar_damp};
-  double *o = h->d_fa_out.p;
-  const FieldAtOut out{o};
-  const double e2s = std::sqrt(h->P.qqrd2e);
-  const ExpCoef K = make_expcoef();
-  CellGrid cg = h->grid;   // (exact mode has built no grid: the kernel takes the box origin from it in both modes)
-  for (int k = 0; k < 3; k++) cg.lo[k] = h->boxlo[k];
+  h->d_fa_out.ensure(8 * (size_t)m);
+  const PointIdx idx = point_upload(h, m, x, skip_atom, molecule);
+  const PointParm pp = point_parm(h);
+  const FieldAtOut out{h->d_fa_out.p};
   const dim3 grid(nblk(m, POLAR_ROWS_PER_BLOCK)), block(POLAR_BLOCK);
   HIPCHECK(hipEventRecord(h->ev_fa[0], s));
-#define FA(AP, D, P)                                                                                                          \
-  k_field_at<AP, D, P><<<grid, block, 0, s>>>(m, h->d_fa_x.p, d_skip, d_pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,    \
-                                              h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, cg,                \
-                                              AP ? nullptr : h->d_cell_first.p, cut, e2s, K, out)
+#define FA(AP, D, P)                                                                                                            \
+  k_field_at<AP, D, P><<<grid, block, 0, s>>>(m, h->d_fa_x.p, idx.skip, idx.pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,  \
+                                              h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, pp.cg,               \
+                                              AP ? nullptr : h->d_cell_first.p, pp.cut, pp.e2s, pp.K, out)
 #define FAP(AP, D) do { if (phi) FA(AP, D, true); else FA(AP, D, false); } while (0)
   if (ap) { if (expd) FAP(true, 0); else FAP(true, 1); }
   else    { if (expd) FAP(false, 0); else FAP(false, 1); }
@@ -1196,14 +1242,7 @@ void field_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom
 #undef FA
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa[1], s));
-  if (e_static) HIPCHECK(hipMemcpyAsync(e_static, out.es(), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (e_induced) HIPCHECK(hipMemcpyAsync(e_induced, out.ei(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (phi_static) HIPCHECK(hipMemcpyAsync(phi_static, out.ps(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (phi_induced) HIPCHECK(hipMemcpyAsync(phi_induced, out.pi(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  float t = 0.f;
-  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
-  if (ms) *ms += (double)t;
+  field_out_finish(h, m, e_static, e_induced, phi_static, phi_induced, false, ms);
 }
 
 // The launch of k_ew_point_real (polar_ewald_field_at.hpp) on the m points in d_fa_x, between the events ev_fa[0] and ev_fa[1],
@@ -1213,14 +1252,9 @@ static void ew_point_real_launch(polar_handle *h, int m, const int *d_skip, cons
   const bool ap = !(st.dd_cutoff > 0.0);
   const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
   hipStream_t s = h->stream;
-  const double rc = st.cut_coul, g = h->P.g_ewald;
-  const PointCut cut{rc * rc, st.dd_cutoff * st.dd_cutoff, 1.0 / (rc * rc), 2.0 / rc, st.polar_damp};
-  const EwPointParm ewp = make_ew_point_parm(g);
+  const PointParm pp = point_parm(h);
+  const EwPointParm ewp = make_ew_point_parm(h->P.g_ewald);
   const FieldAtOut out{h->d_fa_out.p};
-  const double e2s = std::sqrt(h->P.qqrd2e);
-  const ExpCoef K = make_expcoef();
-  CellGrid cg = h->grid;   // (exact mode has built no grid: the kernels take the box origin from it in both modes)
-  for (int k = 0; k < 3; k++) cg.lo[k] = h->boxlo[k];
   if (!h->ew_q_valid) {   // Q of the neutralising-background term, once per call window
     h->d_fa_q.ensure(1);
     k_ew_point_qsum<<<1, 256, 0, s>>>(h->nlocal, h->d_rec0.p, h->d_fa_q.p);
@@ -1231,8 +1265,8 @@ static void ew_point_real_launch(polar_handle *h, int m, const int *d_skip, cons
   HIPCHECK(hipEventRecord(h->ev_fa[0], s));
 #define FA(AP, D, P)                                                                                                               \
   k_ew_point_real<AP, D, P><<<grid, block, 0, s>>>(m, h->d_fa_x.p, d_skip, d_pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,    \
-                                                   h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, cg,                \
-                                                   AP ? nullptr : h->d_cell_first.p, cut, ewp, e2s, K, out)
+                                                   h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, pp.cg,             \
+                                                   AP ? nullptr : h->d_cell_first.p, pp.cut, ewp, pp.e2s, pp.K, out)
 #define FAP(AP, D) do { if (phi) FA(AP, D, true); else FA(AP, D, false); } while (0)
   if (ap) { if (expd) FAP(true, 0); else FAP(true, 1); }
   else    { if (expd) FAP(false, 0); else FAP(false, 1); }
@@ -1251,14 +1285,10 @@ void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *ski
   const bool phi = phi_static || phi_induced || phi_on_device;
   hipStream_t s = h->stream;
   const size_t mm = (size_t)m;
-  h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fa_out.ensure(8 * mm);
-  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
+  h->d_fa_out.ensure(8 * mm);
   if (!h->ev_fa_k.e) h->ev_fa_k.create();
-  HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
-  int *d_skip = nullptr, *d_pmol = nullptr;
-  if (skip_atom) { d_skip = h->d_fa_idx.p; HIPCHECK(hipMemcpyAsync(d_skip, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
-  if (molecule) { d_pmol = h->d_fa_idx.p + mm; HIPCHECK(hipMemcpyAsync(d_pmol, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
-  ew_point_real_launch(h, m, d_skip, d_pmol, phi);
+  const PointIdx idx = point_upload(h, m, x, skip_atom, molecule);
+  ew_point_real_launch(h, m, idx.skip, idx.pmol, phi);
   const double g = h->P.g_ewald, e2s = std::sqrt(h->P.qqrd2e);
   const FieldAtOut out{h->d_fa_out.p};
   const double *lo = h->boxlo;
@@ -1282,16 +1312,7 @@ void ewald_field_at_pass(polar_handle *h, int m, const double *x, const int *ski
   }
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa_k, s));
-  if (e_static) HIPCHECK(hipMemcpyAsync(e_static, out.es(), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (e_induced) HIPCHECK(hipMemcpyAsync(e_induced, out.ei(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (phi_static) HIPCHECK(hipMemcpyAsync(phi_static, out.ps(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (phi_induced) HIPCHECK(hipMemcpyAsync(phi_induced, out.pi(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  float t = 0.f, tk = 0.f;
-  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
-  HIPCHECK(hipEventElapsedTime(&tk, h->ev_fa[1], h->ev_fa_k));
-  h->ew_fa_ms[0] += (double)t; h->ew_fa_ms[1] += (double)tk;
-  if (ms) *ms += (double)t + (double)tk;
+  field_out_finish(h, m, e_static, e_induced, phi_static, phi_induced, true, ms);
 }
 
 // polar_probe_at, one pass.  The field half is a pass of the handle's own field call with no host output: it leaves the points,
@@ -1310,11 +1331,7 @@ void probe_at_pass(polar_handle *h, int m, const double *x, const int *type, con
     if (ewald_on(h)) ewald_field_at_pass(h, m, x, skip_atom, molecule, nullptr, nullptr, nullptr, nullptr, ms, true);
     else field_at_pass(h, m, x, skip_atom, molecule, nullptr, nullptr, nullptr, nullptr, ms, true);
   } else {
-    h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm);
-    if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
-    HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
-    if (skip_atom) HIPCHECK(hipMemcpyAsync(h->d_fa_idx.p, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s));
-    if (molecule) HIPCHECK(hipMemcpyAsync(h->d_fa_idx.p + mm, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s));
+    point_upload(h, m, x, skip_atom, molecule);
   }
   const int *d_skip = skip_atom ? h->d_fa_idx.p : nullptr, *d_pmol = molecule ? h->d_fa_idx.p + mm : nullptr;
   h->d_pr_out.ensure(9 * mm); h->d_pr_qa.ensure(2 * mm); h->d_pr_type.ensure(mm);
@@ -1333,8 +1350,7 @@ void probe_at_pass(polar_handle *h, int m, const double *x, const int *type, con
   HIPCHECK(hipEventRecord(h->ev_fa[0], s));
   if (lj) {
     ProbeGrid pg;
-    pg.g = h->grid;   // (exact mode has built no grid: the kernel takes the box origin from it in both modes)
-    for (int k = 0; k < 3; k++) pg.g.lo[k] = h->boxlo[k];
+    pg.g = point_grid(h);
     pg.ncell_inert = (!ap && h->cell_split) ? h->ncell : 0;
     double width[3];
     box_widths(h->box, width);
@@ -1352,20 +1368,11 @@ void probe_at_pass(polar_handle *h, int m, const double *x, const int *type, con
   }
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa[1], s));
-  if (e_lj) HIPCHECK(hipMemcpyAsync(e_lj, out.elj(), mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (f_lj) HIPCHECK(hipMemcpyAsync(f_lj, out.flj(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (e_total) HIPCHECK(hipMemcpyAsync(e_total, out.et(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (e_coul) HIPCHECK(hipMemcpyAsync(e_coul, out.ec(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (e_pol) HIPCHECK(hipMemcpyAsync(e_pol, out.ep(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  float t = 0.f;
-  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
-  if (ms) *ms += (double)t;
+  point_finish(h, {{e_lj, out.elj(), mm}, {f_lj, out.flj(mm), 3 * mm}, {e_total, out.et(mm), 3 * mm}, {e_coul, out.ec(mm), mm}, {e_pol, out.ep(mm), mm}}, false, ms);
 }
 
-// polar_field_grad_at, one pass: field_at_pass with k_field_grad_at (polar_field_grad_at.hpp) -- the same uploads, cutoffs, e2s,
-// exponential constants and box origin, the events ev_fa[0..1] -- and the block of 18 doubles per point in d_fg_out, where it
-// stays for polar_probe_force_at.  Nothing of the handle's step state is written.
+// polar_field_grad_at, one pass: field_at_pass with k_field_grad_at (polar_field_grad_at.hpp) and the block of 18 doubles per
+// point in d_fg_out, where it stays for polar_probe_force_at.  Nothing of the handle's step state is written.
 void field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *g_static,
                         double *g_induced, double *e_static, double *e_induced, double *ms) {
   const polar_settings &st = h->ph.st;
@@ -1373,38 +1380,22 @@ void field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip
   const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
   hipStream_t s = h->stream;
   const size_t mm = (size_t)m;
-  h->d_fa_x.ensure(3 * mm); h->d_fa_idx.ensure(2 * mm); h->d_fg_out.ensure(POLAR_FIELD_GRAD_DOUBLES * mm);
-  if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
-  HIPCHECK(hipMemcpyAsync(h->d_fa_x.p, x, 3 * mm * sizeof(double), hipMemcpyHostToDevice, s));
-  int *d_skip = nullptr, *d_pmol = nullptr;
-  if (skip_atom) { d_skip = h->d_fa_idx.p; HIPCHECK(hipMemcpyAsync(d_skip, skip_atom, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
-  if (molecule) { d_pmol = h->d_fa_idx.p + mm; HIPCHECK(hipMemcpyAsync(d_pmol, molecule, mm * sizeof(int), hipMemcpyHostToDevice, s)); }
-  const double rc = st.cut_coul;
-  const PointCut cut{rc * rc, st.dd_cutoff * st.dd_cutoff, 1.0 / (rc * rc), 2.0 / rc, st.polar_damp};
+  h->d_fg_out.ensure(POLAR_FIELD_GRAD_DOUBLES * mm);
+  const PointIdx idx = point_upload(h, m, x, skip_atom, molecule);
+  const PointParm pp = point_parm(h);
   const FieldGradOut out{h->d_fg_out.p};
-  const double e2s = std::sqrt(h->P.qqrd2e);
-  const ExpCoef K = make_expcoef();
-  CellGrid cg = h->grid;   // (exact mode has built no grid: the kernel takes the box origin from it in both modes)
-  for (int k = 0; k < 3; k++) cg.lo[k] = h->boxlo[k];
   const dim3 grid(nblk(m, POLAR_ROWS_PER_BLOCK)), block(POLAR_BLOCK);
   HIPCHECK(hipEventRecord(h->ev_fa[0], s));
-#define FG(AP, D)                                                                                                                \
-  k_field_grad_at<AP, D><<<grid, block, 0, s>>>(m, h->d_fa_x.p, d_skip, d_pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,     \
-                                                h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, cg,                 \
-                                                AP ? nullptr : h->d_cell_first.p, cut, e2s, K, out)
+#define FG(AP, D)                                                                                                                  \
+  k_field_grad_at<AP, D><<<grid, block, 0, s>>>(m, h->d_fa_x.p, idx.skip, idx.pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,   \
+                                                h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, pp.cg,                \
+                                                AP ? nullptr : h->d_cell_first.p, pp.cut, pp.e2s, pp.K, out)
   if (ap) { if (expd) FG(true, 0); else FG(true, 1); }
   else    { if (expd) FG(false, 0); else FG(false, 1); }
 #undef FG
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa[1], s));
-  if (e_static) HIPCHECK(hipMemcpyAsync(e_static, out.es(), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (e_induced) HIPCHECK(hipMemcpyAsync(e_induced, out.ei(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (g_static) HIPCHECK(hipMemcpyAsync(g_static, out.gs(mm), 6 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (g_induced) HIPCHECK(hipMemcpyAsync(g_induced, out.gi(mm), 6 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  float t = 0.f;
-  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
-  if (ms) *ms += (double)t;
+  point_finish(h, {{e_static, out.es(), 3 * mm}, {e_induced, out.ei(mm), 3 * mm}, {g_static, out.gs(mm), 6 * mm}, {g_induced, out.gi(mm), 6 * mm}}, false, ms);
 }
 
 // polar_probe_force_at, one pass.  f_lj: a pass of polar_probe_at that asks for nothing but the LJ force (k_probe_lj's FORCE
@@ -1426,12 +1417,7 @@ void probe_force_at_pass(polar_handle *h, int m, const double *x, const int *typ
   k_probe_force_combine<<<nblk(m, 256), 256, 0, s>>>(m, d_q, d_a, std::sqrt(h->P.qqrd2e), out);
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa[1], s));
-  if (f_coul) HIPCHECK(hipMemcpyAsync(f_coul, out.fc(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (f_pol) HIPCHECK(hipMemcpyAsync(f_pol, out.fp(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  float t = 0.f;
-  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
-  if (ms) *ms += (double)t;
+  point_finish(h, {{f_coul, out.fc(mm), 3 * mm}, {f_pol, out.fp(mm), 3 * mm}}, false, ms);
 }
 
 // polar_ewald_field_grid, once per call: the layout from the k-vector table (its rows come back from the device: 16 bytes per
@@ -1508,14 +1494,5 @@ void ewald_field_grid_pass(polar_handle *h, const EwGridCall &c, long long p0, i
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa_k, s));
   if (x_out) HIPCHECK(hipMemcpyAsync(x_out, h->d_fa_x.p, 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (e_static) HIPCHECK(hipMemcpyAsync(e_static, out.es(), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (e_induced) HIPCHECK(hipMemcpyAsync(e_induced, out.ei(mm), 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (phi_static) HIPCHECK(hipMemcpyAsync(phi_static, out.ps(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (phi_induced) HIPCHECK(hipMemcpyAsync(phi_induced, out.pi(mm), mm * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHECK(hipStreamSynchronize(s));
-  float t = 0.f, tk = 0.f;
-  HIPCHECK(hipEventElapsedTime(&t, h->ev_fa[0], h->ev_fa[1]));
-  HIPCHECK(hipEventElapsedTime(&tk, h->ev_fa[1], h->ev_fa_k));
-  h->ew_fa_ms[0] += (double)t; h->ew_fa_ms[1] += (double)tk;
-  if (ms) *ms += (double)t + (double)tk;
+  field_out_finish(h, m, e_static, e_induced, phi_static, phi_induced, true, ms);
 }

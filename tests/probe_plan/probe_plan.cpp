@@ -2,8 +2,8 @@
 //
 // As a shared library (tests/test_probe_plan_host.py): the trimmed stencil of a batch of points, the perpendicular widths and
 // the list grid of a box, the reach table, and the refusals as status codes with their messages.
-// With -DPROBE_PLAN_MAIN a stand-alone program (the sanitizer build): random axes through probe_axis with its invariants
-// checked, and every refusal once.
+// With -DPROBE_PLAN_MAIN a stand-alone program (the sanitizer build): random axes through probe_axis, stencil_axis and
+// seam_part with their invariants checked, and every refusal once.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -46,6 +46,17 @@ void plan_stencil(int n, const double *s, double reach, const double width[3], c
       const polar::ProbeAxis a = polar::probe_axis(s[3 * p + k], reach * scale[k], nc[k]);
       first[3 * p + k] = a.first; count[3 * p + k] = a.count;
     }
+}
+
+// the +-2 rule of centre cell c on an axis of nc cells, and its split at the periodic seam: axis = {first, count}, runs =
+// {first, count} of part 0 and of part 1
+void plan_stencil_axis(int c, int nc, int axis[2], int runs[4]) {
+  const polar::ProbeAxis a = polar::stencil_axis(c, nc);
+  axis[0] = a.first; axis[1] = a.count;
+  for (int part = 0; part < 2; part++) {
+    const polar::ProbeAxis r = polar::seam_part(a, nc, part);
+    runs[2 * part] = r.first; runs[2 * part + 1] = r.count;
+  }
 }
 
 // pack: (ntypes + 1)^2 entries of 8 doubles (pack_lj_table's layout); reach: ntypes + 1 doubles out
@@ -92,6 +103,13 @@ int main(int argc, char **argv) {
       ok = ok && rel < a.count;
     }
     if (!ok) failures++;
+    // ... and the +-2 rule of a cell of the same axis with its seam split: the runs lie on the axis and add up to the count
+    int axis[2], runs[4];
+    plan_stencil_axis((int)(nc * g.uni()), nc, axis, runs);
+    checks++;
+    if (!(axis[0] >= 0 && axis[1] == (nc < 5 ? nc : 5) && runs[0] == axis[0] && runs[1] >= 1 && runs[0] + runs[1] <= nc && runs[2] == 0 &&
+          runs[3] >= 0 && runs[1] + runs[3] == axis[1]))
+      failures++;
   }
   // the refusals, each once, and what is accepted beside them
   const int ty_ok[3] = {1, 2, 2}, ty_lo[3] = {1, 0, 2}, ty_hi[3] = {1, 3, 2};

@@ -7,6 +7,9 @@ For every point: no cell is walked twice; every atom of a seeded set within reac
 in a walked cell, the atom's cell being cell_of's; at reach = cutall at most five cells per axis are walked, at reach <= 0.2
 cutall at most two.
 
+The untrimmed +-2 rule of the other point kernels (stencil_axis) and the split of an x range at the periodic seam (seam_part):
+every axis of 1 to 9 cells, every centre cell.
+
 Reach rule and input checks: every refusal of the header, with the boundary cases width = 2 reach and reach = cutall accepted.
 The same .cpp, as a stand-alone program with its own main, runs under the address and undefined-behaviour sanitizers."""
 import ctypes as C
@@ -45,6 +48,7 @@ def lib(tmp_path_factory):
     L.plan_last_message.restype = C.c_char_p
     L.plan_box.restype, L.plan_box.argtypes = C.c_int, [dp, dp, C.c_int, ip, C.c_double, dp, ip]
     L.plan_stencil.restype, L.plan_stencil.argtypes = None, [C.c_int, dp, C.c_double, dp, ip, ip, ip]
+    L.plan_stencil_axis.restype, L.plan_stencil_axis.argtypes = None, [C.c_int, C.c_int, ip, ip]
     L.plan_reach.restype, L.plan_reach.argtypes = C.c_double, [C.c_int, dp, dp]
     L.plan_check_sites.restype, L.plan_check_sites.argtypes = C.c_int, [C.c_longlong, ip, C.c_int, dp, dp, C.c_int]
     L.plan_check_reach.restype, L.plan_check_reach.argtypes = C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, dp, ip]
@@ -132,6 +136,27 @@ def test_probe_axis_on_its_edges(lib):
     assert first.tolist() == [[0, 1, 4]] and count.tolist() == [[1, 1, 1]]
 
 
+def test_the_five_cell_rule_and_its_seam_split(lib):
+    """stencil_axis and seam_part, which every list-mode walk of polar_point_walk.hpp goes through: for nc = 1 .. 9 and every
+    centre cell, the cells {c-2 .. c+2} mod nc are walked exactly once each (nc < 5: the cells 0 .. nc-1, once each), in at most
+    two runs [first, first + lenA) and [0, count - lenA) that do not overlap."""
+    axis, runs = (C.c_int * 2)(), (C.c_int * 4)()
+    cases = 0
+    for nc in range(1, 10):
+        for c in range(nc):
+            lib.plan_stencil_axis(c, nc, axis, runs)
+            first, count = axis
+            want = sorted(range(nc)) if nc < 5 else sorted((c + o) % nc for o in range(-2, 3))
+            assert 0 <= first < nc and count == len(want), (nc, c, first, count)
+            assert sorted((first + o) % nc for o in range(count)) == want, (nc, c, first, count)
+            (fa, la), (fb, lb) = runs[0:2], runs[2:4]
+            assert fa == first and fb == 0 and la >= 1 and lb >= 0 and la + lb == count, (nc, c, list(runs))
+            assert fa + la <= nc and lb <= fa, (nc, c, list(runs))            # on the axis; the second run ends before the first begins
+            assert sorted(list(range(fa, fa + la)) + list(range(fb, fb + lb))) == want, (nc, c, list(runs))
+            cases += 1
+    assert cases == 45
+
+
 def test_reach_is_the_largest_lj_cutoff_of_the_type(lib):
     nt = 3
     w = nt + 1
@@ -183,4 +208,4 @@ def test_the_same_code_as_a_program_under_the_address_and_undefined_behaviour_sa
     print(r.stdout.strip())
     assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-3000:])
     m = re.match(r"inputs 20000 checks (\d+) failures (\d+)", r.stdout)
-    assert m and int(m.group(1)) == 20000 + 8 + 5 + 1 and int(m.group(2)) == 0, r.stdout
+    assert m and int(m.group(1)) == 2 * 20000 + 8 + 5 + 1 and int(m.group(2)) == 0, r.stdout
