@@ -451,8 +451,8 @@ int polar_probe_at(polar_handle *h, long long npoints, const double *x /*[npoint
  * handle is not disturbed.  The pass buffers (polar_field_at's points and 192 bytes per point of a pass) are freed when the
  * next step begins.
  * Call window and errors are polar_field_at's: POLAR_ERR_STATE outside the window; POLAR_ERR_UNSUPPORTED on a row-sharded handle,
- * with the lab build's tile sweep, in list mode in a box with a non-periodic direction, and with polar_ewald > 0 (the gradient of
- * the real-space erfc part and of the reciprocal part is not built yet); POLAR_ERR_INPUT as polar_field_at. */
+ * with the lab build's tile sweep, in list mode in a box with a non-periodic direction, and with polar_ewald > 0
+ * (polar_ewald_field_grad_at is the call there); POLAR_ERR_INPUT as polar_field_at. */
 int polar_field_grad_at(polar_handle *h, long long npoints, const double *x /*[npoints][3]*/, const int *skip_atom,
                         const int *molecule, double *g_static, double *g_induced /* [npoints][6] each */,
                         double *e_static, double *e_induced /* [npoints][3] each, may be NULL */, double *device_ms);
@@ -469,11 +469,52 @@ int polar_field_grad_at(polar_handle *h, long long npoints, const double *x /*[n
  * LJ pass runs only for f_lj, the gradient pass only for f_coul or f_pol).  Passes, bits, buffers, the wrap of far points and
  * npoints == 0 as above.
  * Call window, POLAR_ERR_UNSUPPORTED and POLAR_ERR_INPUT are polar_probe_at's (the LJ reach rule applies when f_lj is asked
- * for), and POLAR_ERR_UNSUPPORTED with polar_ewald > 0 as for polar_field_grad_at. */
+ * for), and POLAR_ERR_UNSUPPORTED with polar_ewald > 0 (polar_ewald_probe_force_at is the call there). */
 int polar_probe_force_at(polar_handle *h, long long npoints, const double *x /*[npoints][3]*/,
                          const int *type /*[npoints], 1..ntypes*/, const double *q /*[npoints] or NULL = 0*/,
                          const double *alpha /*[npoints] or NULL = 0*/, const int *skip_atom, const int *molecule,
                          double *f_lj, double *f_coul, double *f_pol /*[npoints][3] each*/, double *device_ms);
+
+/* ---- ... and with polar_ewald: the gradient of the Ewald field, and the force in it (extension) -----------
+ * polar_ewald_field_grad_at: polar_ewald_field_at's two fields together with their gradients G_ab = d e_a / d x_b, for handles
+ * with polar_ewald > 0.  Arguments, null rules, units, the component order xx, yy, zz, xy, xz, yz, the passes, the wrap of far
+ * points, the input checks and npoints == 0 are polar_field_grad_at's.  With the notation of polar_ewald_field_at -- d = x_p - x_j
+ * (the mode's image), r = |d|, g = g_ewald, rc = cut_coul, G(r) = 2g/sqrt(pi) e^(-g^2 r^2), ph = erfc(gr)/r for a kept atom and
+ * -erf(gr)/r for an excluded one (the point's molecule, the point's skip_atom, an atom on the point), B1 = (ph + G) / r^2:
+ *   g_static_ab  = e2s [ sum_{r^2 <= rc^2} q_j ( B1 delta_ab - B2 d_a d_b )  +  sum_k c_k k_a k_b Re(e^{ik.p} conj S(k)) ],
+ *                  B2 = (3 B1 + 2 g^2 G(r)) / r^2      (ph' = -r B1, B1' / r = -B2, for the erfc and the erf form alike)
+ *                  an excluded atom at r^2 == 0 (the limit of the erf form; the standard use is a point on its skip_atom):
+ *                  -(2/3) g^2 (2g/sqrt(pi)) q_j on xx, yy and zz, nothing off the diagonal, nothing in the field
+ *                  (an excluded atom within g^2 r^2 < 2^-26 of the point, 3.8e-4 A at g = 0.32, counts as on it: the erf form
+ *                  cancels there in FP64; either way an excluded atom's term is within 1e-7 of its value at any distance)
+ *                  over the step's own half space of k-vectors, c_k and S(k); the neutralising background is a constant of the
+ *                  potential and adds nothing.  Trace: the real-space pair gives -2 g^2 q_j G(r), 4 pi times its screening
+ *                  Gaussian; the whole sum gives -4 pi e2s Q / V (Q = sum of the charges, V the cell volume), zero in a neutral box.
+ *   g_induced_ab = polar_field_grad_at's induced sum, s7 included (`polar_ewald` leaves the dipole tensor cut at the minimum
+ *                  image or at dd_cutoff); nothing from the skip_atom or from an atom at r^2 == 0
+ *   e_static, e_induced: polar_ewald_field_at's, bit for bit, at the same points with the same skip_atom / molecule
+ * g_static does not depend on g_ewald beyond the truncation of the two sums; it jumps by O(erfc(g rc)) across the shell r = rc.
+ * A point's bits depend on the point, the records and the k-vector table alone (no atomics): not on the pass, on the other
+ * points, on their order or on which outputs were asked for.  The handle is not disturbed.  Device memory: polar_field_grad_at's
+ * pass buffers and at most 64 MB of chunk partials (72 bytes per point and chunk of about 1024 k-vectors).
+ * Call window and refusals are polar_ewald_field_at's: POLAR_ERR_STATE outside the window; POLAR_ERR_UNSUPPORTED with
+ * polar_ewald == 0 (polar_field_grad_at is the call there), on a row-sharded handle and with the lab build's tile sweep;
+ * POLAR_ERR_INPUT as polar_field_at.  device_ms and polar_pair_extract "ewald_field_at_ms" (real-space kernel, reciprocal
+ * kernels) are filled as by polar_ewald_field_at. */
+int polar_ewald_field_grad_at(polar_handle *h, long long npoints, const double *x /*[npoints][3]*/, const int *skip_atom,
+                              const int *molecule, double *g_static, double *g_induced /* [npoints][6] each */,
+                              double *e_static, double *e_induced /* [npoints][3] each, may be NULL */, double *device_ms);
+
+/* polar_ewald_probe_force_at: polar_probe_force_at for handles with polar_ewald > 0 -- minus the gradient of polar_probe_at's
+ * e_lj + e_coul + e_pol on such a handle, away from the cutoff shells.  f_lj is polar_probe_at's, bit for bit; f_coul and f_pol
+ * are polar_probe_force_at's expressions on e and G of polar_ewald_field_grad_at at the point.  Arguments, null rules, units,
+ * passes and input checks are polar_probe_force_at's; POLAR_ERR_UNSUPPORTED with polar_ewald == 0 (polar_probe_force_at is the
+ * call there) and wherever polar_probe_at refuses. */
+int polar_ewald_probe_force_at(polar_handle *h, long long npoints, const double *x /*[npoints][3]*/,
+                               const int *type /*[npoints], 1..ntypes*/, const double *q /*[npoints] or NULL = 0*/,
+                               const double *alpha /*[npoints] or NULL = 0*/, const int *skip_atom, const int *molecule,
+                               double *f_lj, double *f_coul, double *f_pol /*[npoints][3] each*/, double *device_ms);
+
 
 
 /* ---- stepwise / sharded interface (multi-GPU driver: one process per GPU, rows sharded) ------

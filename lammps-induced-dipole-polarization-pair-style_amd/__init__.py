@@ -145,6 +145,8 @@ EXPORTS = {
     "polar_probe_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp, _dp]),
     "polar_field_grad_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
     "polar_probe_force_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]),
+    "polar_ewald_field_grad_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _ip, _dp, _dp, _dp, _dp, _dp]),
+    "polar_ewald_probe_force_at": (C.c_int, [C.c_void_p, C.c_longlong, _dp, _ip, _dp, _dp, _ip, _ip, _dp, _dp, _dp, _dp]),
     "polar_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "polar_set_row_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "polar_set_global_count": (C.c_int, [C.c_void_p, C.c_longlong]),
@@ -515,12 +517,7 @@ class PolarPair:
         """``field_at`` for a handle with ``polar_ewald``: the static sums are the Ewald ones (polar_ewald_field_at in
         include/polar_mi355x.h).  The same arguments and the same dict, plus ms_real and ms_recip: the device time of the
         real-space kernel and of the reciprocal kernels."""
-        out = self._field_at(self.L.polar_ewald_field_at, x, skip_atom, molecule, potential)
-        dim = C.c_int()
-        ptr = self.L.polar_pair_extract(self.h, b"ewald_field_at_ms", C.byref(dim))
-        t = C.cast(C.c_void_p(ptr), _dp)
-        out.update(ms_real=t[0], ms_recip=t[1])
-        return out
+        return self._ewald_ms(self._field_at(self.L.polar_ewald_field_at, x, skip_atom, molecule, potential))
 
     def grid_points(self, shape, offset=(0.5, 0.5, 0.5)):
         """The points of ``field_grid``: cell-centred fractional coordinates ((i + 1/2) / nx, (j + 1/2) / ny, (k + 1/2) / nz) of
@@ -627,6 +624,10 @@ class PolarPair:
         include/polar_mi355x.h: formulas, units, when the call is valid); ``skip_atom`` / ``molecule`` as in ``field_at``.
         Returns a dict: g_static, g_induced [m, 6] (xx, yy, zz, xy, xz, yz), e_static, e_induced [m, 3] (the bits of
         ``field_at``; None without ``field``), ms."""
+        return self._field_grad_at(self.L.polar_field_grad_at, x, skip_atom, molecule, field)
+
+    def _field_grad_at(self, entry, x, skip_atom, molecule, field):
+        """the call behind ``field_grad_at`` and ``ewald_field_grad_at``: the two entry points take the same arguments"""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
         m = len(x)
         sk = None if skip_atom is None else np.ascontiguousarray(skip_atom, dtype=np.int32)
@@ -635,16 +636,37 @@ class PolarPair:
         gs, gi = np.zeros((m, 6)), np.zeros((m, 6))
         es, ei = (np.zeros((m, 3)), np.zeros((m, 3))) if field else (None, None)
         ms = C.c_double()
-        self._ck(self.L.polar_field_grad_at(self.h, m, _dptr(x), None if sk is None else _iptr(sk), None if mo is None else _iptr(mo),
-                                            _dptr(gs), _dptr(gi), None if es is None else _dptr(es), None if ei is None else _dptr(ei),
-                                            C.byref(ms)))
+        self._ck(entry(self.h, m, _dptr(x), None if sk is None else _iptr(sk), None if mo is None else _iptr(mo),
+                       _dptr(gs), _dptr(gi), None if es is None else _dptr(es), None if ei is None else _dptr(ei), C.byref(ms)))
         return dict(g_static=gs, g_induced=gi, e_static=es, e_induced=ei, ms=ms.value)
+
+    def _ewald_ms(self, out):
+        """ms_real and ms_recip of the last point call on a handle with ``polar_ewald``, added to its dict"""
+        dim = C.c_int()
+        t = C.cast(C.c_void_p(self.L.polar_pair_extract(self.h, b"ewald_field_at_ms", C.byref(dim))), _dp)
+        out.update(ms_real=t[0], ms_recip=t[1])
+        return out
+
+    def ewald_field_grad_at(self, x, skip_atom=None, molecule=None, field=True):
+        """``field_grad_at`` for a handle with ``polar_ewald``: the gradient of the Ewald field (polar_ewald_field_grad_at in
+        include/polar_mi355x.h); e_static and e_induced have the bits of ``ewald_field_at``.  The same arguments and the same
+        dict, plus ms_real and ms_recip: the device time of the real-space kernel and of the reciprocal kernels."""
+        return self._ewald_ms(self._field_grad_at(self.L.polar_ewald_field_grad_at, x, skip_atom, molecule, field))
 
     def field_grad_grid(self, shape, field=True):
         """``field_grad_at`` on the (nx, ny, nz) grid of ``field_grid`` (``grid_points``); the arrays come back as
         (nz, ny, nx, 6) and (nz, ny, nx, 3)."""
         nx, ny, nz = (int(v) for v in shape)
-        out = self.field_grad_at(self.grid_points((nx, ny, nz)), field=field)
+        return self._grad_grid_shaped(self.field_grad_at(self.grid_points((nx, ny, nz)), field=field), nx, ny, nz)
+
+    def ewald_field_grad_grid(self, shape, field=True, offset=(0.5, 0.5, 0.5)):
+        """``ewald_field_grad_at`` on the grid of ``field_grad_grid``: ``grid_points`` handed to the per-point call, the same
+        shapes.  ``offset`` as in ``ewald_field_grid``."""
+        nx, ny, nz = (int(v) for v in shape)
+        return self._grad_grid_shaped(self.ewald_field_grad_at(self.grid_points((nx, ny, nz), offset), field=field), nx, ny, nz)
+
+    @staticmethod
+    def _grad_grid_shaped(out, nx, ny, nz):
         for k, w in (("g_static", 6), ("g_induced", 6), ("e_static", 3), ("e_induced", 3)):
             if out[k] is not None:
                 out[k] = out[k].reshape(nz, ny, nx, w)
@@ -654,6 +676,15 @@ class PolarPair:
         """The force on test sites at the points ``x`` [m, 3] in the frozen framework (polar_probe_force_at in
         include/polar_mi355x.h); arguments as ``probe_at``.  Returns a dict: f_lj, f_coul, f_pol, force (their sum) [m, 3], ms.
         ``type=None`` skips the LJ part (f_lj = 0); ``q=None`` and ``alpha=None`` together skip the field part."""
+        return self._probe_force_at(self.L.polar_probe_force_at, x, type, q, alpha, skip_atom, molecule)
+
+    def ewald_probe_force_at(self, x, type, q=None, alpha=None, skip_atom=None, molecule=None):
+        """``probe_force_at`` for a handle with ``polar_ewald`` (polar_ewald_probe_force_at in include/polar_mi355x.h): minus
+        the gradient of ``probe_at``'s energy on such a handle.  The same arguments and the same dict."""
+        return self._probe_force_at(self.L.polar_ewald_probe_force_at, x, type, q, alpha, skip_atom, molecule)
+
+    def _probe_force_at(self, entry, x, type, q, alpha, skip_atom, molecule):
+        """the call behind ``probe_force_at`` and ``ewald_probe_force_at``: the two entry points take the same arguments"""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3)
         m = len(x)
         per_point = lambda v, dt: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dt), (m,)))
@@ -664,21 +695,30 @@ class PolarPair:
         ms = C.c_double()
         dptr = lambda a: None if a is None else _dptr(a)
         iptr = lambda a: None if a is None else _iptr(a)
-        self._ck(self.L.polar_probe_force_at(self.h, m, _dptr(x), iptr(ty), dptr(qq), dptr(al), iptr(sk), iptr(mo), _dptr(fl) if lj else None,
-                                             _dptr(fc) if field else None, _dptr(fp) if field else None, C.byref(ms)))
+        self._ck(entry(self.h, m, _dptr(x), iptr(ty), dptr(qq), dptr(al), iptr(sk), iptr(mo), _dptr(fl) if lj else None,
+                       _dptr(fc) if field else None, _dptr(fp) if field else None, C.byref(ms)))
         return dict(f_lj=fl, f_coul=fc, f_pol=fp, force=fl + fc + fp, ms=ms.value)
 
     def insertion_force(self, sites, type, q, alpha, centre=None, molecule=None, skip_atom=None):
         """Net force and torque on trial placements of a rigid guest: ``sites`` [ntrial, nsite, 3] and the other arguments as
         ``insertion_energy``; ``centre`` [ntrial, 3] (or [3]): the point the torque is taken about, by default the mean of the
         trial's sites.  One ``probe_force_at`` call; returns force, torque [ntrial, 3], site_force [ntrial, nsite, 3] and ms."""
+        return self._insertion_force(self.probe_force_at, sites, type, q, alpha, centre, molecule, skip_atom)
+
+    def ewald_insertion_force(self, sites, type, q, alpha, centre=None, molecule=None, skip_atom=None):
+        """``insertion_force`` for a handle with ``polar_ewald``: one ``ewald_probe_force_at`` call, the same arguments and dict."""
+        return self._insertion_force(self.ewald_probe_force_at, sites, type, q, alpha, centre, molecule, skip_atom)
+
+    @staticmethod
+    def _insertion_force(site_forces, sites, type, q, alpha, centre, molecule, skip_atom):
+        """net force and torque of rigid guests from ``site_forces``, the handle's per-site force call"""
         sites = np.ascontiguousarray(sites, dtype=np.float64)
         assert sites.ndim == 3 and sites.shape[2] == 3
         nt, ns = sites.shape[:2]
         per_site = lambda v, dt: None if v is None else np.broadcast_to(np.asarray(v, dtype=dt), (nt, ns)).reshape(-1)
         per_trial = lambda v: None if v is None else np.broadcast_to(np.asarray(v, dtype=np.int32).reshape(-1, 1) if np.ndim(v) else np.asarray(v, dtype=np.int32), (nt, ns)).reshape(-1)
-        out = self.probe_force_at(sites.reshape(-1, 3), per_site(type, np.int32), per_site(q, np.float64), per_site(alpha, np.float64),
-                                  per_trial(skip_atom), per_trial(molecule))
+        out = site_forces(sites.reshape(-1, 3), per_site(type, np.int32), per_site(q, np.float64), per_site(alpha, np.float64),
+                          per_trial(skip_atom), per_trial(molecule))
         f = out["force"].reshape(nt, ns, 3)
         c = sites.mean(axis=1) if centre is None else np.broadcast_to(np.asarray(centre, dtype=np.float64), (nt, 3))
         return dict(force=f.sum(axis=1), torque=np.cross(sites - c[:, None, :], f).sum(axis=1), site_force=f, ms=out["ms"])

@@ -852,7 +852,7 @@ int polar_field_grad_at(polar_handle *h, long long npoints, const double *x, con
                         double *g_static, double *g_induced, double *e_static, double *e_induced, double *device_ms) {
   return guarded(h, [&]() {
     need_device(h);
-    if (ewald_on(h)) throw Unsupported("polar_field_grad_at: not offered with polar_ewald (the gradient of the real-space erfc part and of the reciprocal part is a follow-up)");
+    if (ewald_on(h)) throw Unsupported("polar_field_grad_at: with polar_ewald the static field is not the shifted-force one; polar_ewald_field_grad_at gives the gradient of the Ewald field");
     if (!point_call_begin(h, "polar_field_grad_at", true, npoints, x, skip_atom, device_ms)) return (int)POLAR_OK;
     HIPCHECK(hipSetDevice(h->device));
     point_passes(npoints, [&](long long p0, int m) {
@@ -864,27 +864,58 @@ int polar_field_grad_at(polar_handle *h, long long npoints, const double *x, con
 }
 
 /* ---- ... and the force on a test site: LJ, Coulomb, induction (polar_field_grad_at.hpp, polar_probe_at.hpp) -------- */
+// what polar_probe_force_at and polar_ewald_probe_force_at do behind their refusals: the pass takes the handle's own gradient
+static int probe_force_call(polar_handle *h, const char *name, long long npoints, const double *x, const int *type, const double *q,
+                            const double *alpha, const int *skip_atom, const int *molecule, double *f_lj, double *f_coul, double *f_pol,
+                            double *device_ms) {
+  const polar_settings &st = h->ph.st;
+  const bool lj = f_lj != nullptr, field = f_coul || f_pol;
+  if (!point_call_begin(h, name, true, npoints, x, skip_atom, device_ms)) return (int)POLAR_OK;
+  check_probe_sites(npoints, type, h->ntypes, q, alpha, lj);
+  if (lj) {   // (polar_probe_at's reach check: f_lj is that call's)
+    double width[3];
+    box_widths(h->box, width);
+    check_probe_reach(st.dd_cutoff > 0.0, h->probe_reach_max, st.cut_coul, st.dd_cutoff, width, h->box.periodic);
+  }
+  if (!lj && !field) return (int)POLAR_OK;
+  HIPCHECK(hipSetDevice(h->device));
+  point_passes(npoints, [&](long long p0, int m) {
+    probe_force_at_pass(h, m, x + 3 * p0, from(type, p0), from(q, p0), from(alpha, p0), from(skip_atom, p0), from(molecule, p0),
+                        from(f_lj, p0, 3), from(f_coul, p0, 3), from(f_pol, p0, 3), device_ms);
+  });
+  return (int)POLAR_OK;
+}
 int polar_probe_force_at(polar_handle *h, long long npoints, const double *x, const int *type, const double *q, const double *alpha,
                          const int *skip_atom, const int *molecule, double *f_lj, double *f_coul, double *f_pol, double *device_ms) {
   return guarded(h, [&]() {
     need_device(h);
-    const polar_settings &st = h->ph.st;
-    const bool lj = f_lj != nullptr, field = f_coul || f_pol;
-    if (ewald_on(h)) throw Unsupported("polar_probe_force_at: not offered with polar_ewald (the gradient of the Ewald field is a follow-up)");
-    if (!point_call_begin(h, "polar_probe_force_at", true, npoints, x, skip_atom, device_ms)) return (int)POLAR_OK;
-    check_probe_sites(npoints, type, h->ntypes, q, alpha, lj);
-    if (lj) {   // (polar_probe_at's reach check: f_lj is that call's)
-      double width[3];
-      box_widths(h->box, width);
-      check_probe_reach(st.dd_cutoff > 0.0, h->probe_reach_max, st.cut_coul, st.dd_cutoff, width, h->box.periodic);
-    }
-    if (!lj && !field) return (int)POLAR_OK;
+    if (ewald_on(h)) throw Unsupported("polar_probe_force_at: with polar_ewald the static field is not the shifted-force one; polar_ewald_probe_force_at gives the force in the Ewald field");
+    return probe_force_call(h, "polar_probe_force_at", npoints, x, type, q, alpha, skip_atom, molecule, f_lj, f_coul, f_pol, device_ms);
+  });
+}
+
+/* ---- ... and with polar_ewald: the gradient of the Ewald field and the force in it (polar_ewald_field_grad_at.hpp) -------- */
+int polar_ewald_field_grad_at(polar_handle *h, long long npoints, const double *x, const int *skip_atom, const int *molecule,
+                              double *g_static, double *g_induced, double *e_static, double *e_induced, double *device_ms) {
+  return guarded(h, [&]() {
+    need_device(h);
+    if (!ewald_on(h)) throw Unsupported("polar_ewald_field_grad_at: the handle runs without polar_ewald; polar_field_grad_at gives the gradient of its shifted-force field");
+    if (!point_call_begin(h, "polar_ewald_field_grad_at", false, npoints, x, skip_atom, device_ms)) return (int)POLAR_OK;
     HIPCHECK(hipSetDevice(h->device));
     point_passes(npoints, [&](long long p0, int m) {
-      probe_force_at_pass(h, m, x + 3 * p0, from(type, p0), from(q, p0), from(alpha, p0), from(skip_atom, p0), from(molecule, p0),
-                          from(f_lj, p0, 3), from(f_coul, p0, 3), from(f_pol, p0, 3), device_ms);
+      ewald_field_grad_at_pass(h, m, x + 3 * p0, from(skip_atom, p0), from(molecule, p0), from(g_static, p0, 6), from(g_induced, p0, 6),
+                               from(e_static, p0, 3), from(e_induced, p0, 3), device_ms);
     });
     return (int)POLAR_OK;
+  });
+}
+
+int polar_ewald_probe_force_at(polar_handle *h, long long npoints, const double *x, const int *type, const double *q, const double *alpha,
+                               const int *skip_atom, const int *molecule, double *f_lj, double *f_coul, double *f_pol, double *device_ms) {
+  return guarded(h, [&]() {
+    need_device(h);
+    if (!ewald_on(h)) throw Unsupported("polar_ewald_probe_force_at: the handle runs without polar_ewald; polar_probe_force_at gives the force in its shifted-force field");
+    return probe_force_call(h, "polar_ewald_probe_force_at", npoints, x, type, q, alpha, skip_atom, molecule, f_lj, f_coul, f_pol, device_ms);
   });
 }
 

@@ -552,8 +552,11 @@ void probe_at_pass(polar_handle *h, int m, const double *x, const int *type, con
 // one pass of polar_field_grad_at: as field_at_pass, with the six components of each gradient; the block stays in d_fg_out
 void field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *g_static,
                         double *g_induced, double *e_static, double *e_induced, double *ms);
-// one pass of polar_probe_force_at: f_lj through probe_at_pass, f_coul and f_pol through field_grad_at_pass and
-// k_probe_force_combine
+// the same for polar_ewald_field_grad_at: real-space and induced sums, then the reciprocal sums of the step's k-vectors
+void ewald_field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *g_static,
+                              double *g_induced, double *e_static, double *e_induced, double *ms);
+// one pass of polar_probe_force_at / polar_ewald_probe_force_at: f_lj through probe_at_pass, f_coul and f_pol through the
+// handle's own gradient pass (one of the two above) and k_probe_force_combine
 void probe_force_at_pass(polar_handle *h, int m, const double *x, const int *type, const double *q, const double *alpha,
                          const int *skip_atom, const int *molecule, double *f_lj, double *f_coul, double *f_pol, double *ms);
 // polar_ewald_field_grid: what the passes of a call share -- the grid, the layout of the tables and of the scratch

@@ -44,3 +44,4 @@
 #include "polar_ewald_field_grid.hpp" // ... on a regular grid of the cell (polar_ewald_field_grid)
 #include "polar_probe_at.hpp"         // LJ, Coulomb and induction energy of test sites (polar_probe_at)
 #include "polar_field_grad_at.hpp"    // the field gradient at points and the force on a test site (polar_field_grad_at, polar_probe_force_at)
+#include "polar_ewald_field_grad_at.hpp"   // ... with `polar_ewald`: the gradient of the Ewald field (polar_ewald_field_grad_at, polar_ewald_probe_force_at)

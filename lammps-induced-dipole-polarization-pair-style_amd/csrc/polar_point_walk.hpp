@@ -1,6 +1,7 @@
 // polar_point_walk.hpp -- how a wave finds the candidate records of one caller-supplied point: what the point kernels
-// k_field_at (polar_field_at.hpp), k_field_grad_at (polar_field_grad_at.hpp), k_probe_lj (polar_probe_at.hpp) and
-// k_ew_point_real / k_ew_point_recip (polar_ewald_field_at.hpp) share (k_field_grad_at: all but the list-mode loops).  Part of the hand-written HIP kernels (gfx950 / CDNA4,
+// k_field_at (polar_field_at.hpp), k_field_grad_at (polar_field_grad_at.hpp), k_probe_lj (polar_probe_at.hpp),
+// k_ew_point_real / k_ew_point_recip (polar_ewald_field_at.hpp) and k_ew_grad_real / k_ew_grad_recip (polar_ewald_field_grad_at.hpp)
+// share (k_field_grad_at: all but the list-mode loops).  Part of the hand-written HIP kernels (gfx950 / CDNA4,
 // wave64) of the lj/cut/coul/long/polarization pair style; see polar_kernels.hpp for the mapping and the index spaces.
 //
 // The mapping of all of them is ONE WAVE PER POINT, four consecutive points per 256-thread workgroup (a grid is handed over

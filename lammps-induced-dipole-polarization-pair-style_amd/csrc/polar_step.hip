@@ -1398,16 +1398,67 @@ void field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip
   point_finish(h, {{e_static, out.es(), 3 * mm}, {e_induced, out.ei(mm), 3 * mm}, {g_static, out.gs(mm), 6 * mm}, {g_induced, out.gi(mm), 6 * mm}}, false, ms);
 }
 
-// polar_probe_force_at, one pass.  f_lj: a pass of polar_probe_at that asks for nothing but the LJ force (k_probe_lj's FORCE
-// instance: the bits of that call).  f_coul, f_pol: a gradient pass with no host output, which leaves the block in d_fg_out and
-// has synchronised; then k_probe_force_combine, one thread per point, behind the site's q and alpha.
+// polar_ewald_field_grad_at, one pass: k_ew_grad_real (polar_ewald_field_grad_at.hpp) writes the real-space static sums and
+// the induced sums of the m points into the block of 18 doubles per point in d_fg_out; then, for runs of points sized so that
+// the chunk partials (9 doubles per point and chunk) stay within 64 MB, k_ew_grad_recip over (points, row chunks of the step's
+// k-vector table) and k_ew_grad_fold.  The block stays in d_fg_out for polar_ewald_probe_force_at.  Nothing of the handle's
+// step state is written.
+void ewald_field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *g_static,
+                              double *g_induced, double *e_static, double *e_induced, double *ms) {
+  const polar_settings &st = h->ph.st;
+  const bool ap = !(st.dd_cutoff > 0.0);
+  const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  h->d_fg_out.ensure(POLAR_FIELD_GRAD_DOUBLES * mm);
+  if (!h->ev_fa_k.e) h->ev_fa_k.create();
+  const PointIdx idx = point_upload(h, m, x, skip_atom, molecule);
+  const PointParm pp = point_parm(h);
+  const EwPointParm ewp = make_ew_point_parm(h->P.g_ewald);
+  const FieldGradOut out{h->d_fg_out.p};
+  const dim3 grid(nblk(m, POLAR_ROWS_PER_BLOCK)), block(POLAR_BLOCK);
+  HIPCHECK(hipEventRecord(h->ev_fa[0], s));
+#define FG(AP, D)                                                                                                                 \
+  k_ew_grad_real<AP, D><<<grid, block, 0, s>>>(m, h->d_fa_x.p, idx.skip, idx.pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,   \
+                                               h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, pp.cg,                \
+                                               AP ? nullptr : h->d_cell_first.p, pp.cut, ewp, pp.e2s, pp.K, out)
+  if (ap) { if (expd) FG(true, 0); else FG(true, 1); }
+  else    { if (expd) FG(false, 0); else FG(false, 1); }
+#undef FG
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa[1], s));
+  // reciprocal space
+  const double *lo = h->boxlo;
+  const int nk = h->ew_nk, nrow = nk > 0 ? h->ew_nrow : 0;
+  const int nchunk = ew_point_chunks(nrow, nk), rpc = ew_point_rows_per_chunk(nrow, nk);
+  const size_t per_point = (size_t)std::max(nchunk, 1) * 9 * sizeof(double);
+  const int run = (int)std::max<size_t>(256, std::min<size_t>(mm, ((size_t)64 << 20) / per_point / 256 * 256));
+  h->d_fa_part.ensure((size_t)std::max(nchunk, 1) * 9 * std::min<size_t>(mm, (size_t)run));
+  for (int p0 = 0; p0 < m; p0 += run) {
+    const int np = std::min(run, m - p0);
+    if (nchunk > 0) {
+      const dim3 gk(nblk(np, 256), nchunk);
+      k_ew_grad_recip<<<gk, 256, 0, s>>>(np, p0, h->d_fa_x.p, h->box, lo[0], lo[1], lo[2], ew_cell(h), nrow, rpc, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_fa_part.p);
+      k_ew_grad_fold<<<nblk(np, 256), 256, 0, s>>>(np, p0, m, nchunk, h->d_fa_part.p, pp.e2s, out);
+    }
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa_k, s));
+  point_finish(h, {{e_static, out.es(), 3 * mm}, {e_induced, out.ei(mm), 3 * mm}, {g_static, out.gs(mm), 6 * mm}, {g_induced, out.gi(mm), 6 * mm}}, true, ms);
+}
+
+// polar_probe_force_at and polar_ewald_probe_force_at, one pass.  f_lj: a pass of polar_probe_at that asks for nothing but the
+// LJ force (k_probe_lj's FORCE instance: the bits of that call).  f_coul, f_pol: a gradient pass of the handle's own model with
+// no host output, which leaves the block in d_fg_out and has synchronised; then k_probe_force_combine, one thread per point,
+// behind the site's q and alpha.
 void probe_force_at_pass(polar_handle *h, int m, const double *x, const int *type, const double *q, const double *alpha,
                          const int *skip_atom, const int *molecule, double *f_lj, double *f_coul, double *f_pol, double *ms) {
   hipStream_t s = h->stream;
   const size_t mm = (size_t)m;
   if (f_lj) probe_at_pass(h, m, x, type, nullptr, nullptr, skip_atom, molecule, nullptr, nullptr, nullptr, f_lj, nullptr, ms);
   if (!f_coul && !f_pol) return;
-  field_grad_at_pass(h, m, x, skip_atom, molecule, nullptr, nullptr, nullptr, nullptr, ms);
+  if (ewald_on(h)) ewald_field_grad_at_pass(h, m, x, skip_atom, molecule, nullptr, nullptr, nullptr, nullptr, ms);
+  else field_grad_at_pass(h, m, x, skip_atom, molecule, nullptr, nullptr, nullptr, nullptr, ms);
   h->d_pr_qa.ensure(2 * mm);
   const double *d_q = nullptr, *d_a = nullptr;
   if (f_coul && q) { d_q = h->d_pr_qa.p; HIPCHECK(hipMemcpyAsync(h->d_pr_qa.p, q, mm * sizeof(double), hipMemcpyHostToDevice, s)); }
