@@ -60,17 +60,31 @@ def _excluded(mol, I, J):
     return (mol[I] == mol[J]) & (mol[I] != 0)
 
 
-def field(x, q, mol, H, cut, g, accuracy, e2s=1.0, parts=False):
-    """Static field E_i (times e2s): real space + exclusion correction + reciprocal space."""
+def _kblocks(nk, kblock):
+    """slices of at most kblock k-vectors (the dense [n, nk] phase arrays of a large box would not fit in memory)"""
+    return [slice(a, min(nk, a + kblock)) for a in range(0, nk, kblock)]
+
+
+def field(x, q, mol, H, cut, g, accuracy, e2s=1.0, parts=False, kblock=None):
+    """Static field E_i (times e2s): real space + exclusion correction + reciprocal space.
+    kblock: the reciprocal sum in blocks of that many k-vectors (S(k) of a block needs all atoms and no other k: the same
+    terms, the partial sums of the blocks added in order); None, the default: all k-vectors at once."""
     x = np.asarray(x, np.float64)
     I, J, d, r2 = _pairs(x, H, cut)
     b1, _ = _b12(r2, g, ~_excluded(mol, I, J))
     ereal = np.zeros_like(x)
     np.add.at(ereal, I, (b1 * q[J])[:, None] * d)
     k, c = kvectors(H, g, accuracy)
-    ph = x @ k.T                                        # [n, nk]
-    S = (q[:, None] * np.exp(1j * ph)).sum(0)
-    erec = (np.imag(np.exp(1j * ph) * np.conj(S)[None, :]) * c[None, :]) @ k
+    if kblock is None:
+        ph = x @ k.T                                        # [n, nk]
+        S = (q[:, None] * np.exp(1j * ph)).sum(0)
+        erec = (np.imag(np.exp(1j * ph) * np.conj(S)[None, :]) * c[None, :]) @ k
+    else:
+        erec = np.zeros_like(x)
+        for b in _kblocks(len(k), kblock):
+            e = np.exp(1j * (x @ k[b].T))
+            S = (q[:, None] * e).sum(0)
+            erec += (np.imag(e * np.conj(S)[None, :]) * c[None, b]) @ k[b]
     if parts:
         return e2s * ereal, e2s * erec
     return e2s * (ereal + erec)
@@ -81,9 +95,10 @@ def energy(x, q, mol, mu, H, cut, g, accuracy, e2s=1.0):
     return -np.sum(mu * field(x, q, mol, H, cut, g, accuracy, e2s))
 
 
-def forces_virial(x, q, mol, mu, H, cut, g, accuracy, e2s=1.0, parts=False):
+def forces_virial(x, q, mol, mu, H, cut, g, accuracy, e2s=1.0, parts=False, kblock=None):
     """Analytic forces -dU/dx at fixed mu and the virial [xx, yy, zz, xy, xz, yz] in LAMMPS' convention (sum r_a F_b).
-    parts=True: (real-space forces, reciprocal forces, pairwise real-space virial, reciprocal virial) instead."""
+    parts=True: (real-space forces, reciprocal forces, pairwise real-space virial, reciprocal virial) instead.
+    kblock: as in field()."""
     x = np.asarray(x, np.float64)
     I, J, d, r2 = _pairs(x, H, cut)
     b1, b2 = _b12(r2, g, ~_excluded(mol, I, J))
@@ -94,22 +109,28 @@ def forces_virial(x, q, mol, mu, H, cut, g, accuracy, e2s=1.0, parts=False):
     f = np.zeros_like(x)
     np.add.at(f, I, fp)
     w = 0.5 * np.einsum("pa,pb->ab", d, fp)            # every pair seen from both atoms
-    k, c = kvectors(H, g, accuracy)
-    e = np.exp(1j * (x @ k.T))
-    S = (q[:, None] * e).sum(0)
-    kmu = mu @ k.T
-    M = (kmu * e).sum(0)
-    res = np.real(e * np.conj(S)[None, :])
-    rem = np.real(e * np.conj(M)[None, :])
+    k_all, c_all = kvectors(H, g, accuracy)
     f_real, w_real = f.copy(), w.copy()
-    f_rec = e2s * ((kmu * res - q[:, None] * rem) * c[None, :]) @ k
+    f_rec = None
+    for b in ([slice(None)] if kblock is None else _kblocks(len(k_all), kblock)):
+        k, c = k_all[b], c_all[b]
+        e = np.exp(1j * (x @ k.T))
+        S = (q[:, None] * e).sum(0)
+        kmu = mu @ k.T
+        M = (kmu * e).sum(0)
+        res = np.real(e * np.conj(S)[None, :])
+        rem = np.real(e * np.conj(M)[None, :])
+        f_blk = e2s * ((kmu * res - q[:, None] * rem) * c[None, :]) @ k
+        f_rec = f_blk if f_rec is None else f_rec + f_blk
+        erec = e2s * (np.imag(e * np.conj(S)[None, :]) * c[None, :]) @ k
+        U = -e2s * c * np.imag(M * np.conj(S))
+        k2 = np.einsum("ij,ij->i", k, k)
+        bb = 2 * (1 / k2 + 1 / (4 * g * g))
+        w += np.einsum("k,ab->ab", U, np.eye(3)) - np.einsum("k,ka,kb->ab", U * bb, k, k)
+        w -= np.einsum("ia,ib->ab", mu, erec)
+    if f_rec is None:
+        f_rec = np.zeros_like(x)
     f += f_rec
-    erec = e2s * (np.imag(e * np.conj(S)[None, :]) * c[None, :]) @ k
-    U = -e2s * c * np.imag(M * np.conj(S))
-    k2 = np.einsum("ij,ij->i", k, k)
-    bb = 2 * (1 / k2 + 1 / (4 * g * g))
-    w += np.einsum("k,ab->ab", U, np.eye(3)) - np.einsum("k,ka,kb->ab", U * bb, k, k)
-    w -= np.einsum("ia,ib->ab", mu, erec)
     six = lambda m: np.array([m[0, 0], m[1, 1], m[2, 2], m[0, 1], m[0, 2], m[1, 2]])  # noqa: E731
     if parts:
         return f_real, f_rec, six(w_real), six(w) - six(w_real)

@@ -136,6 +136,45 @@ def test_energy_forces_virial_against_numpy_and_oracle(mode, wl, pkg, oracle):
     assert out["iterations"] == it
 
 
+def test_two_tiles_per_chunk_against_numpy_and_oracle(wl, pkg, oracle, tmp_path):
+    """The handle's own k-space launches where a chunk of k_ew_sfac takes two tiles: MOF-5 + H2 (1,349 atoms), list mode,
+    g_ewald 0.6, polar_ewald 1e-12.  The plan (through the probe's host entry, tests/ewald_kspace_load.py) gives 35,855
+    k-vectors, nm = 25, tiles of 32 atoms and chunks of 45: a tile of 32 and one of 13 per chunk, the second trip of the tile
+    loop that the 60-atom systems above never take; k_ew_force runs 6 workgroups and writes f through d_perm.  (The kernels
+    alone, at every tiling, against long double: tests/test_gpu_ewald_kspace.py.)
+
+    ef_static against the NumPy field, f / u_ef / eng_pol / the vflag = 1 virial against oracle + NumPy as in
+    test_energy_forces_virial_against_numpy_and_oracle, with this file's tolerances (1e-10, 1e-9).  The NumPy sums run in
+    blocks of 2,048 k-vectors (kblock: the dense [n, nk] arrays would take several GB) and cost about 6 s of CPU."""
+    import ewald_kspace_load as kl
+    acc = "1e-12"
+    s, _ = wl.load_fixture(os.path.join(GOLD, "mof5_h2.npz"), g_ewald=0.6,
+                           extra_args=["dd_cutoff", "12.8345", "polar_ewald", acc, "use_previous", "no", "precision", "1e-13",
+                                       "max_iterations", "200"])
+    n = s.nlocal
+    pl = kl.load(pkg, tmp_path).plan(s.prd, (0.0, 0.0, 0.0), s.g_ewald, float(acc), n)
+    assert (pl["nk"], pl["nm"], pl["tile"], pl["chunk"]) == (35855, 25, 32, 45)
+    assert pl["tile"] < pl["chunk"] <= 2 * pl["tile"] and (n + 255) // 256 == 6
+    out = _run(pkg, s, eflag=1, vflag=1)
+    assert out["status"] == 0 and out["nkvec"] == pl["nk"]
+    e2s, H, kb = np.sqrt(s.qqrd2e), _H(s), 2048
+    E = ew.field(s.x[:n], s.q[:n], s.molecule[:n], H, s.settings.cut_coul, s.g_ewald, float(acc), e2s, kblock=kb)
+    assert np.max(np.abs(out["ef_static"] - E)) < 1e-10 * np.max(np.abs(E))
+    mu = out["mu"]
+    f_lj, v_lj, _, _, f_dd, res = _oracle_parts(oracle, s, mu)
+    f_q, v_q = ew.forces_virial(s.x[:n], s.q[:n], s.molecule[:n], mu, H, s.settings.cut_coul, s.g_ewald, float(acc), e2s, kblock=kb)
+    u_ef = -float(np.sum(mu * E))
+    eng_pol = res.u_self + res.u_dd + u_ef
+    assert abs(out["eng_pol"] - eng_pol) < 1e-9 * abs(eng_pol)
+    assert abs(out["u_ef"] - u_ef) < 1e-9 * abs(u_ef)
+    f_ref = oracle.fold_ghost_forces(f_lj + f_dd, s.owner, n)
+    f_ref += f_q
+    f_dev = oracle.fold_ghost_forces(out["f"], s.owner, n)
+    assert np.max(np.abs(f_dev - f_ref)) < 1e-9 * np.max(np.abs(f_ref))
+    v_ref = v_lj + np.array(res.virial) + v_q
+    assert np.max(np.abs(out["virial"] - v_ref)) < 1e-9 * np.max(np.abs(v_ref))
+
+
 @pytest.mark.parametrize("route", ["fdotr_half_list", "fdotr_full_list"])
 def test_fdotr_virial_with_the_reciprocal_terms(route, wl, pkg, oracle):
     """vflag = 2: the fdotr virial over the pair forces (locals and ghosts with LAMMPS' half list; with the device-built full
