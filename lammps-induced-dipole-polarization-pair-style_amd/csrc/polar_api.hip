@@ -941,6 +941,28 @@ int polar_ewald_field_grid(polar_handle *h, const int n[3], const double offset[
   });
 }
 
+/* ---- ... and the gradient of that field on the grid: nine coefficient sets through the transforms (polar_ewald_field_grad_grid.hpp) -------- */
+int polar_ewald_field_grad_grid(polar_handle *h, const int n[3], const double offset[3], double *x_out, double *g_static, double *g_induced,
+                                double *e_static, double *e_induced, double *device_ms) {
+  return guarded(h, [&]() {
+    need_device(h);
+    if (!ewald_on(h)) throw Unsupported("polar_ewald_field_grad_grid: the handle runs without polar_ewald; polar_field_grad_at gives the gradient of its shifted-force field");
+    point_call_state(h, "polar_ewald_field_grad_grid");
+    double off[3];
+    const long long npoints = check_grid(n, offset, off);
+    if (device_ms) *device_ms = 0.0;
+    h->ew_fa_ms[0] = h->ew_fa_ms[1] = 0.0;
+    HIPCHECK(hipSetDevice(h->device));
+    EwGridCall call;
+    ewald_field_grad_grid_begin(h, n, off, call, device_ms);
+    point_passes(npoints, [&](long long p0, int m) {
+      ewald_field_grad_grid_pass(h, call, p0, m, from(x_out, p0, 3), from(g_static, p0, 6), from(g_induced, p0, 6), from(e_static, p0, 3),
+                                 from(e_induced, p0, 3), device_ms);
+    });
+    return (int)POLAR_OK;
+  });
+}
+
 /* ---- stepwise / sharded interface (multi-GPU driver, parallel.py) --------------------------- */
 int polar_set_stream(polar_handle *h, void *hip_stream) {
   return guarded(h, [&]() {

@@ -326,8 +326,8 @@ struct polar_handle {
   bool ew_q_valid = false;
   Event ev_fa_k;
   double ew_fa_ms[2] = {0.0, 0.0};
-  // polar_ewald_field_grid (polar_ewald_field_grid.hpp): the phase tables and T of a call, V of a run of lines (at most 64 MB),
-  // the first row of every h (freed with the pass buffers)
+  // polar_ewald_field_grid (polar_ewald_field_grid.hpp) and polar_ewald_field_grad_grid (polar_ewald_field_grad_grid.hpp): the
+  // phase tables and T of a call, V of a run of lines (at most 64 MB), the first row of every h (freed with the pass buffers)
   DBuf<double2> d_eg_tab, d_eg_t, d_eg_v;
   DBuf<int> d_eg_first;
   // polar_probe_at (polar_probe_at.hpp): the host copy of the packed LJ table and the reach of every type in it (upload_types:
@@ -572,6 +572,11 @@ struct EwGridCall {
 void ewald_field_grid_begin(polar_handle *h, const int n[3], const double off[3], EwGridCall &c, double *ms);
 void ewald_field_grid_pass(polar_handle *h, const EwGridCall &c, long long p0, int m, double *x_out, double *e_static, double *e_induced,
                            double *phi_static, double *phi_induced, double *ms);
+// polar_ewald_field_grad_grid: the same two steps with the nine coefficient sets of polar_ewald_grid_grad.hpp in T and V (the
+// buffers of polar_ewald_field_grid, sized for them), k_ew_grad_real for the real-space and induced sums and the block in d_fg_out
+void ewald_field_grad_grid_begin(polar_handle *h, const int n[3], const double off[3], EwGridCall &c, double *ms);
+void ewald_field_grad_grid_pass(polar_handle *h, const EwGridCall &c, long long p0, int m, double *x_out, double *g_static,
+                                double *g_induced, double *e_static, double *e_induced, double *ms);
 // ---- polar_color.hip --------------------------------------------------------------------------------------------------
 void ensure_colors(polar_handle *h);
 struct ColorComm {   // what a distributed colouring needs from the transport (polar_dist.hip)

@@ -27,6 +27,8 @@
 // polar_ewald_field_at.hpp (`polar_ewald_field_at`: the same map for `polar_ewald` handles, real-space and reciprocal sums;
 // arithmetic in the plain-C++ polar_ewald_point.hpp) and polar_ewald_field_grid.hpp (`polar_ewald_field_grid`: that map on a
 // regular grid of the cell, the reciprocal sums as three 1-D transforms; arithmetic in the plain-C++ polar_ewald_grid.hpp).
+// polar_ewald_field_grad_grid.hpp (`polar_ewald_field_grad_grid`) does the same for the gradient map of
+// polar_ewald_field_grad_at.hpp, with nine coefficient sets; arithmetic in the plain-C++ polar_ewald_grid_grad.hpp.
 // The point kernels of these and of polar_probe_at.hpp / polar_field_grad_at.hpp find a point's candidate records by ONE walk,
 // polar_point_walk.hpp (the wrap into the box, every record in exact mode, a cell stencil in list mode).
 #pragma once
@@ -45,3 +47,4 @@
 #include "polar_probe_at.hpp"         // LJ, Coulomb and induction energy of test sites (polar_probe_at)
 #include "polar_field_grad_at.hpp"    // the field gradient at points and the force on a test site (polar_field_grad_at, polar_probe_force_at)
 #include "polar_ewald_field_grad_at.hpp"   // ... with `polar_ewald`: the gradient of the Ewald field (polar_ewald_field_grad_at, polar_ewald_probe_force_at)
+#include "polar_ewald_field_grad_grid.hpp" // ... on a regular grid of the cell, nine coefficient sets through the three 1-D transforms (polar_ewald_field_grad_grid)

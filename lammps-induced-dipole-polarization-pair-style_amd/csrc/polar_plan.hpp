@@ -211,15 +211,16 @@ inline EwGridPlan ew_grid_plan(const PlanI4 *rows, int nrow) {
 }
 // Table and scratch sizes of a call on an (nx, ny, nz) grid, in entries of 16 bytes (one complex number): the three phase
 // tables in one array (x at 0, y at off_y, z at off_z, `tab` in all), T[nrow][nz][4], and the bytes of V per line,
-// (hmax + 1) x 4 sets.
+// (hmax + 1) x 4 sets.  nset: the coefficient sets per element of T and V -- 4 for polar_ewald_field_grid, 9 (EW_GG_SETS of
+// polar_ewald_grid_grad.hpp) for polar_ewald_field_grad_grid: T[nrow][nz][nset], (hmax + 1) x nset x 16 bytes of V per line.
 struct EwGridSizes { size_t off_y, off_z, tab, t, v_line_bytes; };
-inline EwGridSizes ew_grid_sizes(const EwGridPlan &p, int nrow, const int n[3]) {
+inline EwGridSizes ew_grid_sizes(const EwGridPlan &p, int nrow, const int n[3], int nset = 4) {
   EwGridSizes s;
   s.off_y = (size_t)(p.hmax + 1) * (size_t)n[0];
   s.off_z = s.off_y + (size_t)(2 * p.kmax + 1) * (size_t)n[1];
   s.tab = s.off_z + (size_t)(2 * p.lmax + 1) * (size_t)n[2];
-  s.t = (size_t)nrow * (size_t)n[2] * 4;
-  s.v_line_bytes = (size_t)(p.hmax + 1) * 4 * 16;
+  s.t = (size_t)nrow * (size_t)n[2] * (size_t)nset;
+  s.v_line_bytes = (size_t)(p.hmax + 1) * (size_t)nset * 16;
   return s;
 }
 // whole lines of the grid whose V fits the 64 MB that the per-point path spends on its chunk partials (at least one)

@@ -1398,28 +1398,20 @@ void field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip
   point_finish(h, {{e_static, out.es(), 3 * mm}, {e_induced, out.ei(mm), 3 * mm}, {g_static, out.gs(mm), 6 * mm}, {g_induced, out.gi(mm), 6 * mm}}, false, ms);
 }
 
-// polar_ewald_field_grad_at, one pass: k_ew_grad_real (polar_ewald_field_grad_at.hpp) writes the real-space static sums and
-// the induced sums of the m points into the block of 18 doubles per point in d_fg_out; then, for runs of points sized so that
-// the chunk partials (9 doubles per point and chunk) stay within 64 MB, k_ew_grad_recip over (points, row chunks of the step's
-// k-vector table) and k_ew_grad_fold.  The block stays in d_fg_out for polar_ewald_probe_force_at.  Nothing of the handle's
-// step state is written.
-void ewald_field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *g_static,
-                              double *g_induced, double *e_static, double *e_induced, double *ms) {
+// The launch of k_ew_grad_real (polar_ewald_field_grad_at.hpp) on the m points in d_fa_x, between the events ev_fa[0] and ev_fa[1],
+// into the block in d_fg_out: what polar_ewald_field_grad_at and polar_ewald_field_grad_grid share.
+static void ew_grad_real_launch(polar_handle *h, int m, const int *d_skip, const int *d_pmol) {
   const polar_settings &st = h->ph.st;
   const bool ap = !(st.dd_cutoff > 0.0);
   const bool expd = st.damping_type == POLAR_DAMP_EXPONENTIAL;
   hipStream_t s = h->stream;
-  const size_t mm = (size_t)m;
-  h->d_fg_out.ensure(POLAR_FIELD_GRAD_DOUBLES * mm);
-  if (!h->ev_fa_k.e) h->ev_fa_k.create();
-  const PointIdx idx = point_upload(h, m, x, skip_atom, molecule);
   const PointParm pp = point_parm(h);
   const EwPointParm ewp = make_ew_point_parm(h->P.g_ewald);
   const FieldGradOut out{h->d_fg_out.p};
   const dim3 grid(nblk(m, POLAR_ROWS_PER_BLOCK)), block(POLAR_BLOCK);
   HIPCHECK(hipEventRecord(h->ev_fa[0], s));
 #define FG(AP, D)                                                                                                                 \
-  k_ew_grad_real<AP, D><<<grid, block, 0, s>>>(m, h->d_fa_x.p, idx.skip, idx.pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,   \
+  k_ew_grad_real<AP, D><<<grid, block, 0, s>>>(m, h->d_fa_x.p, d_skip, d_pmol, h->sorted ? h->d_inv.p : nullptr, h->nlocal,       \
                                                h->d_scal.p, h->d_rec0.p, h->d_rec1.p, h->d_mol_s.p, h->box, pp.cg,                \
                                                AP ? nullptr : h->d_cell_first.p, pp.cut, ewp, pp.e2s, pp.K, out)
   if (ap) { if (expd) FG(true, 0); else FG(true, 1); }
@@ -1427,6 +1419,23 @@ void ewald_field_grad_at_pass(polar_handle *h, int m, const double *x, const int
 #undef FG
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa[1], s));
+}
+
+// polar_ewald_field_grad_at, one pass: k_ew_grad_real (polar_ewald_field_grad_at.hpp) writes the real-space static sums and
+// the induced sums of the m points into the block of 18 doubles per point in d_fg_out; then, for runs of points sized so that
+// the chunk partials (9 doubles per point and chunk) stay within 64 MB, k_ew_grad_recip over (points, row chunks of the step's
+// k-vector table) and k_ew_grad_fold.  The block stays in d_fg_out for polar_ewald_probe_force_at.  Nothing of the handle's
+// step state is written.
+void ewald_field_grad_at_pass(polar_handle *h, int m, const double *x, const int *skip_atom, const int *molecule, double *g_static,
+                              double *g_induced, double *e_static, double *e_induced, double *ms) {
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  h->d_fg_out.ensure(POLAR_FIELD_GRAD_DOUBLES * mm);
+  if (!h->ev_fa_k.e) h->ev_fa_k.create();
+  const PointIdx idx = point_upload(h, m, x, skip_atom, molecule);
+  ew_grad_real_launch(h, m, idx.skip, idx.pmol);
+  const double e2s = std::sqrt(h->P.qqrd2e);
+  const FieldGradOut out{h->d_fg_out.p};
   // reciprocal space
   const double *lo = h->boxlo;
   const int nk = h->ew_nk, nrow = nk > 0 ? h->ew_nrow : 0;
@@ -1439,7 +1448,7 @@ void ewald_field_grad_at_pass(polar_handle *h, int m, const double *x, const int
     if (nchunk > 0) {
       const dim3 gk(nblk(np, 256), nchunk);
       k_ew_grad_recip<<<gk, 256, 0, s>>>(np, p0, h->d_fa_x.p, h->box, lo[0], lo[1], lo[2], ew_cell(h), nrow, rpc, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_fa_part.p);
-      k_ew_grad_fold<<<nblk(np, 256), 256, 0, s>>>(np, p0, m, nchunk, h->d_fa_part.p, pp.e2s, out);
+      k_ew_grad_fold<<<nblk(np, 256), 256, 0, s>>>(np, p0, m, nchunk, h->d_fa_part.p, e2s, out);
     }
   }
   HIPCHECK(hipGetLastError());
@@ -1471,10 +1480,12 @@ void probe_force_at_pass(polar_handle *h, int m, const double *x, const int *typ
   point_finish(h, {{f_coul, out.fc(mm), 3 * mm}, {f_pol, out.fp(mm), 3 * mm}}, false, ms);
 }
 
-// polar_ewald_field_grid, once per call: the layout from the k-vector table (its rows come back from the device: 16 bytes per
-// (h, k) row), then the phase tables (k_ew_grid_tab) and stage 1 (k_ew_grid_l) of polar_ewald_field_grid.hpp.  Their device
-// time is reciprocal time.
-void ewald_field_grid_begin(polar_handle *h, const int n[3], const double off[3], EwGridCall &c, double *ms) {
+// polar_ewald_field_grid and polar_ewald_field_grad_grid (`name`), once per call: the layout from the k-vector table (its rows
+// come back from the device: 16 bytes per (h, k) row) with nset coefficient sets per element of T and V, then the phase tables
+// (k_ew_grid_tab) and stage 1 -- k_ew_grid_l of polar_ewald_field_grid.hpp with four sets, k_ew_gg_l of
+// polar_ewald_field_grad_grid.hpp with EW_GG_SETS.  Their device time is reciprocal time.
+static void ew_grid_call_begin(polar_handle *h, const std::string &name, int nset, const int n[3], const double off[3], EwGridCall &c,
+                               double *ms) {
   hipStream_t s = h->stream;
   const int nk = h->ew_nk, nrow = nk > 0 ? h->ew_nrow : 0;
   std::vector<PlanI4> rows((size_t)nrow + 1, PlanI4{0, 0, 0, 0});
@@ -1483,24 +1494,26 @@ void ewald_field_grid_begin(polar_handle *h, const int n[3], const double off[3]
     HIPCHECK(hipStreamSynchronize(s));
   }
   c.plan = ew_grid_plan(rows.data(), nrow);
-  if (!c.plan.ok) throw std::runtime_error("polar_ewald_field_grid: the k-vector table is not in (h, k) order");
+  if (!c.plan.ok) throw std::runtime_error(name + ": the k-vector table is not in (h, k) order");
   EwGrid &g = c.g;
   for (int a = 0; a < 3; a++) { g.n[a] = n[a]; g.off[a] = off[a]; g.lo[a] = h->boxlo[a]; }
   g.ax = h->box.prd[0]; g.bx = h->box.xy; g.by = h->box.prd[1]; g.cx = h->box.xz; g.cy = h->box.yz; g.cz = h->box.prd[2];
   ew_grid_slo(h->ew_cell, h->boxlo, g.slo);
-  c.sz = ew_grid_sizes(c.plan, nrow, n);
+  c.sz = ew_grid_sizes(c.plan, nrow, n, nset);
   c.lines_per_run = ew_grid_lines_per_run(c.sz.v_line_bytes);
   const int nzb = nblk(n[2], 64);
   if ((long long)nrow * nzb > 2147483647LL || (c.sz.tab + 255) / 256 > (size_t)2147483647)
-    throw InputError("polar_ewald_field_grid: the grid is too large for the k-vector table's stage-1 launch");
+    throw InputError(name + ": the grid is too large for the k-vector table's stage-1 launch");
   h->d_eg_tab.ensure(c.sz.tab); h->d_eg_t.ensure(c.sz.t); h->d_eg_first.ensure(c.plan.first.size());
   if (!h->ev_fa[0].e) { h->ev_fa[0].create(); h->ev_fa[1].create(); }
   if (!h->ev_fa_k.e) h->ev_fa_k.create();
   HIPCHECK(hipMemcpyAsync(h->d_eg_first.p, c.plan.first.data(), c.plan.first.size() * sizeof(int), hipMemcpyHostToDevice, s));
   HIPCHECK(hipEventRecord(h->ev_fa[1], s));
   k_ew_grid_tab<<<(unsigned)((c.sz.tab + 255) / 256), 256, 0, s>>>(c.sz.tab, g, c.plan.kmax, c.plan.lmax, c.sz.off_y, c.sz.off_z, h->d_eg_tab.p);
-  if (nrow > 0)
-    k_ew_grid_l<<<nrow * nzb, 64, 0, s>>>(nrow, n[2], nzb, c.plan.lmax, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_eg_tab.p + c.sz.off_z, h->d_eg_t.p);
+  if (nrow > 0) {
+    if (nset == EW_GG_SETS) k_ew_gg_l<<<nrow * nzb, 64, 0, s>>>(nrow, n[2], nzb, c.plan.lmax, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_eg_tab.p + c.sz.off_z, h->d_eg_t.p);
+    else                    k_ew_grid_l<<<nrow * nzb, 64, 0, s>>>(nrow, n[2], nzb, c.plan.lmax, h->d_ew_rows.p, h->d_ew_kv.p, h->d_ew_s.p, h->d_eg_tab.p + c.sz.off_z, h->d_eg_t.p);
+  }
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipEventRecord(h->ev_fa_k, s));
   HIPCHECK(hipStreamSynchronize(s));   // (c.plan.first has gone up)
@@ -1508,6 +1521,12 @@ void ewald_field_grid_begin(polar_handle *h, const int n[3], const double off[3]
   HIPCHECK(hipEventElapsedTime(&tk, h->ev_fa[1], h->ev_fa_k));
   h->ew_fa_ms[1] += (double)tk;
   if (ms) *ms += (double)tk;
+}
+void ewald_field_grid_begin(polar_handle *h, const int n[3], const double off[3], EwGridCall &c, double *ms) {
+  ew_grid_call_begin(h, "polar_ewald_field_grid", 4, n, off, c, ms);
+}
+void ewald_field_grad_grid_begin(polar_handle *h, const int n[3], const double off[3], EwGridCall &c, double *ms) {
+  ew_grid_call_begin(h, "polar_ewald_field_grad_grid", EW_GG_SETS, n, off, c, ms);
 }
 
 // ... and one pass, the points [p0, p0 + m) of the flat order: k_ew_grid_points writes them into d_fa_x, k_ew_point_real adds
@@ -1546,4 +1565,40 @@ void ewald_field_grid_pass(polar_handle *h, const EwGridCall &c, long long p0, i
   HIPCHECK(hipEventRecord(h->ev_fa_k, s));
   if (x_out) HIPCHECK(hipMemcpyAsync(x_out, h->d_fa_x.p, 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
   field_out_finish(h, m, e_static, e_induced, phi_static, phi_induced, true, ms);
+}
+
+// polar_ewald_field_grad_grid, one pass, the points [p0, p0 + m) of the flat order: k_ew_grid_points writes them into d_fa_x,
+// k_ew_grad_real adds the real-space static sums and the induced sums into the block in d_fg_out as for
+// polar_ewald_field_grad_at; then, per run of whole lines whose V -- nine sets -- stays within 64 MB (ew_grid_runs), stage 2
+// (k_ew_gg_k) and stage 3 with the fold (k_ew_gg_h) of polar_ewald_field_grad_grid.hpp.  T and V live in the buffers of
+// polar_ewald_field_grid (d_eg_*: the two calls do not overlap).  Nothing of the handle's step state is written.
+void ewald_field_grad_grid_pass(polar_handle *h, const EwGridCall &c, long long p0, int m, double *x_out, double *g_static,
+                                double *g_induced, double *e_static, double *e_induced, double *ms) {
+  hipStream_t s = h->stream;
+  const size_t mm = (size_t)m;
+  h->d_fa_x.ensure(3 * mm); h->d_fg_out.ensure(POLAR_FIELD_GRAD_DOUBLES * mm);
+  k_ew_grid_points<<<nblk(m, 256), 256, 0, s>>>(m, p0, c.g, h->d_fa_x.p);
+  HIPCHECK(hipGetLastError());
+  ew_grad_real_launch(h, m, nullptr, nullptr);
+  const double e2s = std::sqrt(h->P.qqrd2e);
+  const FieldGradOut out{h->d_fg_out.p};
+  const int nx = c.g.n[0], ny = c.g.n[1], nz = c.g.n[2], hmax = c.plan.hmax;
+  const std::vector<EwGridRun> runs = ew_grid_runs(p0, m, nx, c.lines_per_run);
+  long long nl_max = 1;
+  for (const EwGridRun &r : runs) nl_max = std::max(nl_max, r.lb - r.la);
+  h->d_eg_v.ensure((size_t)nl_max * (size_t)(hmax + 1) * EW_GG_SETS);
+  const int nyb = nblk(ny, 64), nxb = nblk(nx, 64);
+  for (const EwGridRun &r : runs) {
+    const int nl = (int)(r.lb - r.la), gz0 = (int)(r.la / ny), ngz = (int)((r.lb - 1) / ny) - gz0 + 1;
+    const long long bk = (long long)(hmax + 1) * ngz * nyb, bh = (long long)nl * nxb;
+    if (bk > 2147483647LL || bh > 2147483647LL) throw InputError("polar_ewald_field_grad_grid: a run of lines is too large for one launch");
+    k_ew_gg_k<<<(unsigned)bk, 64, 0, s>>>(r.la, r.lb, gz0, ngz, nyb, nz, ny, c.plan.kmax, h->d_eg_first.p, h->d_ew_rows.p, h->d_eg_t.p,
+                                         h->d_eg_tab.p + c.sz.off_y, h->d_eg_v.p);
+    if (e_static) k_ew_gg_h<true><<<(unsigned)bh, 64, 0, s>>>(r.q0, r.q1, r.la, nl, nx, nxb, hmax, h->d_eg_v.p, h->d_eg_tab.p, p0, m, e2s, out);
+    else          k_ew_gg_h<false><<<(unsigned)bh, 64, 0, s>>>(r.q0, r.q1, r.la, nl, nx, nxb, hmax, h->d_eg_v.p, h->d_eg_tab.p, p0, m, e2s, out);
+  }
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord(h->ev_fa_k, s));
+  if (x_out) HIPCHECK(hipMemcpyAsync(x_out, h->d_fa_x.p, 3 * mm * sizeof(double), hipMemcpyDeviceToHost, s));
+  point_finish(h, {{e_static, out.es(), 3 * mm}, {e_induced, out.ei(mm), 3 * mm}, {g_static, out.gs(mm), 6 * mm}, {g_induced, out.gi(mm), 6 * mm}}, true, ms);
 }
